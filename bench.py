@@ -523,6 +523,23 @@ def timed_steps(step, drain, fence, warmup, steps, on_timed_start=None):
     return elapsed, out, gathered
 
 
+DUMP_BUDGET = 60 * 10**6   # bytes of core data per --dump-outputs (64 MB in all with the .npy headers)
+
+
+def dump_outputs(path, t):
+    """The rounded cores of one step, as a caller receives them: core k of the sampled items -> path/core<k>.npy.  The sample
+    is a fixed function of the batch size (seeded permutation, as many items as fit into DUMP_BUDGET, in batch order)."""
+    import numpy as np
+
+    B = t.cores[0].shape[0]
+    per_item = sum(c[0].numel() * c.element_size() for c in t.cores)
+    n = max(1, min(B, DUMP_BUDGET // per_item))
+    idx = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:n].sort().values
+    os.makedirs(path, exist_ok=True)
+    for k, c in enumerate(t.cores):
+        np.save(os.path.join(path, f"core{k}.npy"), c.index_select(0, idx.to(c.device)).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -548,7 +565,14 @@ def main():
     ap.add_argument("--single-stream", action="store_true",
                     help="issue the timed region on one stream too (for rocprofv3 kernel traces: with sub-batch "
                          "streams the traced kernel durations overlap)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rounded cores of the last step as DIR/core<k>.npy (float32, "
+                         "[items, r_k, 64, r_k+1]) for a fixed seeded sample of the batch items, at most 64 MB in all (rank 0's batch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.config != "metric":
+        ap.error("--dump-outputs: the metric workload only")
     if args.config != "metric":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_configs
@@ -648,6 +672,8 @@ def main():
 
     elapsed, out, gathered = timed_steps(step, drain, fence, args.warmup, args.steps, on_timed_start=lambda: setattr(sched, "g0", sched.gathers))
     sched.gathers_timed = sched.gathers - getattr(sched, "g0", 0)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     if dist_on:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

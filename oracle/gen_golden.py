@@ -341,6 +341,28 @@ def case_producers():
                            "ref": "tensor.py:687-773, 2309-2320; tools.py:460-512", "dtype": "float64"}, **groups)
 
 
+def case_patch_reference():
+    """The reference's own answers behind tests/test_patch_reference.py: Tensor.round_tt(eps=1e-8) of g + g (tensor.py:2008-2083),
+    and tn.reduce (tools.py:460-512) with an order-sensitive combiner on 1..9 tensors."""
+    torch.set_default_dtype(torch.float64)
+    torch.manual_seed(4)
+    g = tn.rand([6, 7, 5, 8, 6], ranks_tt=4)
+    t = g + g
+    r = t.clone()
+    r.round_tt(eps=1e-8)
+    groups = {"unpatched_inp": npl(t.cores), "unpatched_out": npl(r.cores)}
+    torch.manual_seed(6)
+    for count in range(1, 10):
+        ts = [tn.randn([4, 5, 3], ranks_tt=2) for _ in range(count)]
+        for j, x in enumerate(ts):
+            groups[f"reduce{count}_t{j}"] = npl(x.cores)
+        red = tn.reduce([x.clone() for x in ts], lambda a, b: a + b * 2.0, eps=1e-12)
+        groups[f"reduce{count}_dense"] = red.torch().numpy()
+    save("patch_reference_f64", {"what": "t=g+g, g=tn.rand([6,7,5,8,6], ranks_tt=4), t.round_tt(eps=1e-8); "
+                                         "tn.reduce(count randn [4,5,3] rank-2 TTs, lambda a, b: a + b * 2.0, eps=1e-12), count 1..9",
+                                 "ref": "tensor.py:2008-2083; tools.py:460-512", "dtype": "float64"}, **groups)
+
+
 def case_consumers():
     """tools.shift_mode (tools.py:650-697) and matrix.TTMatrix construction / torch() / trace() (matrix.py:23-175)."""
     torch.set_default_dtype(torch.float64)
@@ -392,7 +414,7 @@ def case_known_answers():
 
 CASES = [case_round_eps_f64, case_round_rmax_f32, case_round_batch_f64, case_dense_f64, case_dense_batch_f32, case_c0,
          case_truncated_svd, case_orthogonalize, case_round_tucker, case_ctor_tucker, case_round_general, case_cp_als, case_cp_variants,
-         case_producers, case_consumers, case_known_answers]
+         case_producers, case_patch_reference, case_consumers, case_known_answers]
 
 if __name__ == "__main__":
     # no arguments: regenerate everything; otherwise only the named cases (the CP-ALS case is reproducible only

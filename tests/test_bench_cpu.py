@@ -114,3 +114,32 @@ def test_per_kind_roofline_is_on_executed_work():
     sw = bench.sweep_executed(pk, 10.0)
     assert sw["kinds"] == ["qr_factor", "rotgram"] and sw["flops_per_step"] > 0
     assert bench.headline_roofline(pk, "eigh", prof, steps)["frac"] is None
+
+
+def test_dump_outputs_is_a_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: core k of a seeded sample of batch items -> DIR/core<k>.npy, same items on every call, within the budget."""
+    import numpy as np
+    import torch
+
+    torch.manual_seed(0)
+    cores = [torch.randn(50, 1, 6, 3), torch.randn(50, 3, 6, 2), torch.randn(50, 2, 6, 1)]
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 10 * sum(c[0].numel() * 4 for c in cores) + 7)   # room for 10 of the 50 items
+    t = type("T", (), {"cores": cores})()
+    bench.dump_outputs(str(tmp_path / "a"), t)
+    bench.dump_outputs(str(tmp_path / "b"), t)
+    idx = None
+    for k, c in enumerate(cores):
+        a, b = np.load(tmp_path / "a" / f"core{k}.npy"), np.load(tmp_path / "b" / f"core{k}.npy")
+        assert a.dtype == np.float32 and a.shape == (10,) + tuple(c.shape[1:]) and np.array_equal(a, b)
+        rows = [next(i for i in range(50) if np.array_equal(c[i].numpy(), x)) for x in a]
+        assert rows == sorted(rows) and (idx is None or rows == idx)
+        idx = rows
+    assert sum(os.path.getsize(f) for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET + 128 * len(cores)
+
+
+def test_steps_must_be_positive(monkeypatch):
+    import pytest
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.main()

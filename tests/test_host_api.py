@@ -26,7 +26,8 @@ def test_golden_round(alg):
     g = load_case("round_eps_f64")
     t = tn.round_tt(tn.Tensor(g["inp"]), eps=1e-8, algorithm=alg)
     assert t.ranks_tt.tolist() == [1, 4, 4, 4, 4, 4, 4, 4, 1]
-    assert _max_abs(t.cores, g[alg]) < 1e-9
+    # up to the per-bond sign of the singular vectors, which LAPACK builds choose differently ('eig': MKL's code paths differ)
+    assert _max_abs(oracle.gauge_align(g[alg], t.cores), g[alg]) < 1e-9
     g = load_case("round_batch_f64")
     t = tn.Tensor(g["inp"], batch=True)
     t.round_tt(rmax=2, algorithm=alg)

@@ -11,12 +11,18 @@ def _max_abs(a, b):
     return max((x - y).abs().max().item() for x, y in zip(a, b))
 
 
+def _max_rel_per_core(a, b):
+    """Largest entry-wise difference of a core, in units of that core's largest reference entry (worst core)."""
+    return max(((x - y).abs().max() / y.abs().max()).item() for x, y in zip(a, b))
+
+
 @pytest.mark.parametrize("alg", ["svd", "eig"])
 def test_round_eps_f64(alg):
     g = load_case("round_eps_f64")
     out = oracle.round_tt(g["inp"], eps=1e-8, algorithm=alg)
     assert oracle.tt_ranks(out) == oracle.tt_ranks(g[alg])
-    assert _max_abs(out, g[alg]) < 1e-9
+    # up to the per-bond sign of the singular vectors, which LAPACK builds choose differently ('eig': MKL's code paths differ)
+    assert _max_abs(oracle.gauge_align(g[alg], out), g[alg]) < 1e-9
 
 
 @pytest.mark.parametrize("alg", ["svd", "eig"])
@@ -24,7 +30,8 @@ def test_round_rmax_f32(alg):
     g = load_case("round_rmax_f32")
     out = oracle.round_tt(g["inp"], rmax=3, algorithm=alg)
     assert oracle.tt_ranks(out) == [1, 3, 3, 3, 3, 1]
-    assert _max_abs(out, g[alg]) < 2e-3  # float32 LAPACK, flat randn spectrum
+    # float32 LAPACK, flat randn spectrum: MKL's instruction-set code paths land up to ~2.4e-6 of a core's scale apart
+    assert _max_rel_per_core(oracle.gauge_align(g[alg], out), g[alg]) < 1e-5
     assert (oracle.tt_to_dense(out) - oracle.tt_to_dense(g[alg])).norm() / oracle.tt_to_dense(g[alg]).norm() < 1e-4
 
 

@@ -1,9 +1,8 @@
-"""``tntorch_amd.patch(tntorch)`` on the reference's own class: the bodies of the reference's
-tests/test_round.py:7-68 run through the patched methods.  CPU box: the real reference from /root/reference, host
-mirror underneath.  GPU box (no /root/reference there): a minimal stand-in class with the reference's attributes,
-device cores, HIP kernels underneath."""
-import os
-import sys
+"""``tntorch_amd.patch(tntorch)`` on a class shaped like the reference's own: the bodies of the reference's
+tests/test_round.py:7-68 run through the patched methods.  The patched object is a minimal stand-in with the reference's
+attributes (tensor.py:107-209) whose own methods refuse to run, so every call the bodies make lands in this package: CPU cores
+on the host mirror, device cores on the HIP kernels.  What the reference itself answers (its unpatched round_tt, its reduce
+tree) comes from tests/golden/patch_reference_f64.npz, recorded by oracle/gen_golden.py."""
 import types
 
 import numpy as np
@@ -12,18 +11,81 @@ import torch
 
 import oracle
 import tntorch_amd as tna
+from parity import load_case
 
-REF = "/root/reference"
+
+class _RefLike:
+    """The attributes / construction the reference's Tensor exposes on this path (tensor.py:107-209), plus the helpers the
+    reference's tests use around the patched methods (``clone``, ``dim``, ``ranks_tt``, ``torch``, ``+``, scalar ``/``)."""
+
+    def __init__(self, cores, Us=None, idxs=None, batch=False):
+        self.cores = list(cores)
+        self.Us = [None] * len(cores) if Us is None else list(Us)
+        self.idxs = idxs
+        self.batch = batch
+
+    @classmethod
+    def _of(cls, t):
+        return cls(t.cores, t.Us, t.idxs, t.batch)
+
+    def _ours(self):
+        return tna.Tensor(list(self.cores), Us=list(self.Us), idxs=self.idxs, batch=self.batch)
+
+    def clone(self):
+        return _RefLike([c.clone() for c in self.cores], [None if U is None else U.clone() for U in self.Us], self.idxs, self.batch)
+
+    def dim(self):
+        return len(self.cores)
+
+    @property
+    def ranks_tt(self):
+        return self._ours().ranks_tt
+
+    def torch(self):
+        return self._ours().torch()
+
+    def __add__(self, other):
+        return _RefLike._of(self._ours() + other._ours())
+
+    def __truediv__(self, s):
+        return _RefLike._of(self._ours() / s)
+
+    # unpatched placeholders (the reference's own methods would sit here)
+    def round_tt(self, *a, **k):
+        raise AssertionError("unpatched")
+
+    orthogonalize = left_orthogonalize = right_orthogonalize = round_tucker = round = factor_orthogonalize = round_tt
+
+
+def _unpatched_truncated_svd(*a, **k):
+    raise AssertionError("unpatched")
+
+
+def _stand_in_module():
+    """The names of the reference module the test bodies reach: ``Tensor`` and ``truncated_svd`` (what ``patch`` rebinds),
+    ``rand``, ``relative_error`` and the free ``round_tt`` (round.py:7-19: clone, then the method)."""
+
+    def rand(shape, ranks_tt=None, ranks_tucker=None):
+        if ranks_tt is None and ranks_tucker is None:
+            ranks_tucker = [None] * len(shape)  # the reference's default: full TT ranks (create.py:243-272)
+        return _RefLike._of(tna.rand(shape, ranks_tt=ranks_tt, ranks_tucker=ranks_tucker))
+
+    def relative_error(gt, approx):
+        a, b = gt.torch(), approx.torch()
+        return (a - b).norm() / a.norm()
+
+    def round_tt(t, *a, **k):
+        t = t.clone()
+        t.round_tt(*a, **k)
+        return t
+
+    return types.SimpleNamespace(Tensor=_RefLike, truncated_svd=_unpatched_truncated_svd, rand=rand,
+                                 relative_error=relative_error, round_tt=round_tt)
 
 
 @pytest.fixture()
 def ref_tn():
-    if not os.path.isdir(os.path.join(REF, "tntorch")):
-        pytest.skip("reference tree not present")
-    sys.dont_write_bytecode = True
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    import tntorch as tn
+    tn = _stand_in_module()
     saved = torch.get_default_dtype()
     torch.set_default_dtype(torch.float64)  # tests/test_round.py:4
     undo = tna.patch(tn)
@@ -113,39 +175,19 @@ def test_reference_round_tucker_body(ref_tn):
 
 
 def test_patched_result_equals_unpatched(ref_tn):
-    """Same input through the reference's own code and through the patched class: identical ranks, same tensor."""
+    """Same input through the patched class and through the reference's own method (its output recorded): identical ranks,
+    same tensor."""
     tn = ref_tn
-    torch.manual_seed(4)
-    g = tn.rand([6, 7, 5, 8, 6], ranks_tt=4)
-    t = g + g
-    a = t.clone()
+    g = load_case("patch_reference_f64")
+    a = tn.Tensor(g["unpatched_inp"])
     a.round_tt(eps=1e-8)                                        # patched (host mirror)
-    b = t.clone()
-    tn.Tensor.round_tt._tntorch_amd_original(b, eps=1e-8)       # the reference's own method
-    assert list(a.ranks_tt) == list(b.ranks_tt)
-    assert (a.torch() - b.torch()).norm() / b.torch().norm() < 1e-12
+    b = g["unpatched_out"]                                      # the reference's own method
+    assert list(a.ranks_tt) == oracle.tt_ranks(b)
+    ref = oracle.tt_to_dense(b)
+    assert (a.torch() - ref).norm() / ref.norm() < 1e-12
 
 
-# ------------------------------------------------------------------ GPU box: stand-in for the reference class
-class _RefLike:
-    """The attributes / construction the reference's Tensor exposes on this path (tensor.py:107-209)."""
-
-    def __init__(self, cores, Us=None, idxs=None, batch=False):
-        self.cores = list(cores)
-        self.Us = [None] * len(cores) if Us is None else list(Us)
-        self.idxs = idxs
-        self.batch = batch
-
-    def clone(self):
-        return _RefLike([c.clone() for c in self.cores], [None if U is None else U.clone() for U in self.Us], self.idxs, self.batch)
-
-    # unpatched placeholders (the reference's own methods would sit here)
-    def round_tt(self, *a, **k):
-        raise AssertionError("unpatched")
-
-    orthogonalize = left_orthogonalize = right_orthogonalize = round_tucker = round = factor_orthogonalize = round_tt
-
-
+# ------------------------------------------------------------------ device cores under the stand-in class
 @pytest.mark.gpu
 def test_patch_on_device_cores():
     mod = types.SimpleNamespace(Tensor=_RefLike, truncated_svd=None)
@@ -179,22 +221,16 @@ def test_patch_on_device_cores():
 
 def test_reduce_tree_matches_reference_order():
     """tools.reduce (own implementation) builds the same tree and hands the operands over in the same order as
-    tools.py:460-512: checked with a non-commutative combiner on 1..9 tensors against the unpatched reference."""
-    if not os.path.isdir(os.path.join(REF, "tntorch")):
-        pytest.skip("reference tree not present")
-    sys.dont_write_bytecode = True
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    import tntorch as tn
-    torch.manual_seed(6)
+    tools.py:460-512: checked with a non-commutative combiner on 1..9 tensors against the reference's recorded results."""
+    g = load_case("patch_reference_f64")
     for count in range(1, 10):
-        cores = [oracle.tt_randn([4, 5, 3], 2, dtype=torch.float64) for _ in range(count)]
+        cores = [g[f"reduce{count}_t{j}"] for j in range(count)]
 
         def comb(a, b):
             return a + b * 2.0  # order-sensitive: every tree shape / operand order gives different weights
 
-        ref = tn.reduce([tn.Tensor([c.clone() for c in cs]) for cs in cores], comb, eps=1e-12)
+        ref = g[f"reduce{count}_dense"]
         ours = tna.reduce((tna.Tensor([c.clone() for c in cs]) for cs in cores), comb, eps=1e-12)  # a generator works too
-        assert (ours.torch() - ref.torch()).norm() / ref.torch().norm() < 1e-10, count
+        assert (ours.torch() - ref).norm() / ref.norm() < 1e-10, count
     with pytest.raises(ValueError):
         tna.reduce([], comb)
