@@ -53,9 +53,9 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
-#define TTR_ABI_VERSION 11
+#define TTR_ABI_VERSION 12
 int ttr_version(void);
 const char* ttr_last_error(void);
 
@@ -675,6 +675,31 @@ int ttr_prof_collect(double* ms, int64_t* launches);
  * `rows32` and pass-through flags), by tiny kernels enqueued outside the timed scopes.  Instrumented: qr_factor, qr_apply (flops),
  * rowgram, rotgram, project (flops and bytes), gemm (flops and bytes of the dense product).  Synchronises the device; resets. */
 int ttr_prof_collect_work(double* flops, double* bytes);
+
+
+/*
+ * Batched TT point evaluation (ABI 12): the index-array block of tensor.py:1019-1434 (`t[idx_matrix]`, `t[:, [..], [..]]`).
+ * For a contiguous block of `nmodes` cores G_n (batched [B, r_n, I_n, r_{n+1}], element strides core_strides[4n .. 4n+3] =
+ * batch, r, I, r') and one index column per mode (P entries, element stride idx_strides[n], int32 (idx_dtype 0) or int64 (1),
+ * negative entries wrap as in torch):
+ *     out[b, :, p, :] = G_0[b][:, i_0[p], :] @ G_1[b][:, i_1[p], :] @ ... @ G_{nmodes-1}[b][:, i_{nmodes-1}[p], :]
+ * (r_0 x r_nmodes), written at out + b*stride_ob + i*stride_or + p*stride_op + j*stride_oc -- the reference's [r_a, P, r_b] core.
+ * Replaces: the per-mode `einsum("iaj,jak->iak")` chain over gathered slices, tensor.py:1357-1378.
+ * `ranks` (nmodes + 1 entries), `sizes`, `cores`, `core_strides`, `idx`, `idx_strides` are HOST arrays (of device pointers).
+ * Points are grouped by index value with a device counting sort per mode, and each slice is multiplied against the 64 running-
+ * product rows of a tile that share it; P <= direct_max_points (< 0: library default, 1024) skips the sort (one tile per point).
+ * Both paths give bitwise identical values, and a point's value does not depend on the other points of the call.
+ * Every index is validated on the device first: the int32 word at `oob_flag` (device) is set to 1 when an index lies outside
+ * [-I_n, I_n), and to 0 otherwise; when set, nothing else is written.  The caller reads the word after the call.
+ * Ranks <= 512, batch <= 65535.
+ */
+int64_t ttr_gather_chain_workspace_bytes(int dtype, int64_t nmodes, const int64_t* ranks, const int64_t* sizes, int64_t P,
+                                         int64_t batch);
+int ttr_gather_chain(int dtype, int64_t nmodes, int64_t batch, int64_t P, const int64_t* ranks, const int64_t* sizes,
+                     const void* const* cores, const int64_t* core_strides, int idx_dtype, const void* const* idx,
+                     const int64_t* idx_strides, void* out, int64_t stride_ob, int64_t stride_or, int64_t stride_op,
+                     int64_t stride_oc, int64_t direct_max_points, void* oob_flag, void* workspace, int64_t workspace_bytes,
+                     void* stream);
 
 #ifdef __cplusplus
 }

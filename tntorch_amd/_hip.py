@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TTR_LIB_PATH") or os.path.join(_HERE, "libttround_hip.so")
 
 F32, F64 = 0, 1
-ABI_VERSION = 11  # include/ttround_hip.h: TTR_ABI_VERSION
+ABI_VERSION = 12  # include/ttround_hip.h: TTR_ABI_VERSION
 SCALE_NONE, SCALE_MUL, SCALE_DIV = 0, 1, 2
 EIG_RAW, EIG_REF, EIG_MATCH_DIAG = 0, 1, 2
 SOLVER_JACOBI_REL, SOLVER_JACOBI_ABS, SOLVER_TRIDIAG, SOLVER_JACOBI_LIVE = 0, 1, 2, 3  # `abs_floor` argument of ttr_eigh_trunc
@@ -184,6 +184,12 @@ _SIGNATURES = {
         c_int,
         [c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_void_p,
          c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
+    "ttr_gather_chain_workspace_bytes": (c_int64, [c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64]),
+    "ttr_gather_chain": (
+        c_int,
+        [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p],
     ),
     "ttr_debug_set_qr_stamps": (c_int, [c_void_p]),
     "ttr_debug_set_knob": (c_int, [c_int, c_int]),
@@ -1060,6 +1066,47 @@ def core_kron(a: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     _, S1, _, S2 = c.shape
     out = torch.empty((B, R1 * S1, I, R2 * S2), dtype=a.dtype, device=a.device)
     _check(L.ttr_core_kron(dt, B, R1, S1, I, R2, S2, a.data_ptr(), c.data_ptr(), out.data_ptr(), _stream()), "ttr_core_kron")
+    return out
+
+
+@_on_device
+def gather_chain(cores, idx, out: Optional[torch.Tensor] = None, direct_max_points: int = -1) -> torch.Tensor:
+    """ttr_gather_chain: cores [B, r_n, I_n, r_{n+1}] (any strides), one device index column (int32 / int64, length P, any
+    stride) per core -> ``out`` [B, r_0, P, r_N] (fresh, or a given [B, r_0, P, r_N] tensor of any strides).  Raises IndexError
+    when an index lies outside its mode (read from the device word the call sets; nothing else is written then)."""
+    L = lib()
+    n = len(cores)
+    assert n >= 1 and len(idx) == n
+    dt = dtype_code(cores[0].dtype)
+    dev = cores[0].device
+    B = cores[0].shape[0]
+    P = idx[0].shape[0]
+    for k in range(n):
+        c = cores[k]
+        assert c.dim() == 4 and c.dtype == cores[0].dtype and c.device == dev and c.shape[0] == B
+        assert k == 0 or c.shape[1] == cores[k - 1].shape[3], "ttr_gather_chain: ranks do not match"
+        assert idx[k].dim() == 1 and idx[k].shape[0] == P and idx[k].device == dev
+    if any(i.dtype != idx[0].dtype for i in idx) or idx[0].dtype not in (torch.int32, torch.int64):
+        idx = [i.to(torch.int64) for i in idx]
+    ranks = (c_int64 * (n + 1))(*([int(c.shape[1]) for c in cores] + [int(cores[-1].shape[3])]))
+    sizes = (c_int64 * n)(*[int(c.shape[2]) for c in cores])
+    ptrs = (c_void_p * n)(*[c.data_ptr() for c in cores])
+    strides = (c_int64 * (4 * n))(*[int(s) for c in cores for s in c.stride()])
+    iptrs = (c_void_p * n)(*[i.data_ptr() for i in idx])
+    istr = (c_int64 * n)(*[int(i.stride(0)) for i in idx])
+    if out is None:
+        out = torch.empty((B, ranks[0], P, ranks[n]), dtype=cores[0].dtype, device=dev)
+    assert tuple(out.shape) == (B, ranks[0], P, ranks[n]) and out.dtype == cores[0].dtype
+    wsb = L.ttr_gather_chain_workspace_bytes(dt, n, ranks, sizes, P, B)
+    if wsb < 0:
+        raise ValueError("ttr_gather_chain_workspace_bytes: bad arguments")
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    _check(L.ttr_gather_chain(dt, n, B, P, ranks, sizes, ptrs, strides, 1 if idx[0].dtype == torch.int64 else 0, iptrs, istr,
+                              out.data_ptr(), *[int(s) for s in out.stride()], int(direct_max_points), flag.data_ptr(),
+                              ws.data_ptr(), wsb, _stream()), "ttr_gather_chain")
+    if int(flag.item()):  # the one host read of the call
+        raise IndexError("index out of range: an index array entry lies outside its mode")
     return out
 
 

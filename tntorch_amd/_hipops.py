@@ -1816,3 +1816,13 @@ def core_kron(a4: torch.Tensor, b4: torch.Tensor) -> torch.Tensor:
 def scale(x: torch.Tensor, value: float) -> torch.Tensor:
     """x * value for a device tensor of any shape (ttr_scale_batch with one broadcast scalar)."""
     return _hip.scale_batch(x.reshape(1, -1), scale=float(value)).reshape(x.shape)
+
+
+def mm(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """[B, m, k] @ [B, k, n] on the matrix cores (ttr_gemm)."""
+    return _hip.gemm(A, B)
+
+
+def gather_chain(cores4: Sequence[torch.Tensor], idx: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Index-array block of tensor.py:1357-1378 (ttr_gather_chain): [B, r_0, P, r_N]; IndexError when an index is out of range."""
+    return _hip.gather_chain(list(cores4), list(idx))

@@ -407,3 +407,17 @@ def core_kron(a4: torch.Tensor, b4: torch.Tensor) -> torch.Tensor:
 
 def scale(x: torch.Tensor, value) -> torch.Tensor:
     return x * value
+
+
+def mm(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """[B, m, k] @ [B, k, n] (joins of integer-indexed slices, tensor.py:1114-1138, 1335-1345)."""
+    return _mm(A, B)
+
+
+def gather_chain(cores4: Sequence[torch.Tensor], idx: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Index-array block of tensor.py:1357-1378: cores [B, r_n, I_n, r_{n+1}] and one index vector per core ->
+    [B, r_0, P, r_N], out[b, :, p, :] = prod_n cores[n][b, :, idx[n][p], :]."""
+    X = cores4[0][:, :, idx[0], :]
+    for c, i in zip(cores4[1:], idx[1:]):
+        X = torch.einsum("biaj,bjak->biak", X, c[:, :, i, :])
+    return X

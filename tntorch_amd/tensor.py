@@ -364,6 +364,18 @@ class Tensor(object):
                 Us.append(None if self.Us[n] is None else (self.Us[n].clone() if _clone else self.Us[n]))
         return Tensor(self._denorm(cores), Us=Us, idxs=self._idxs, batch=self.batch)
 
+    # ------------------------------------------------------------------ indexing (tensor.py:1019-1434)
+    def __getitem__(self, key):
+        """NumPy-style indexing: ints, slices, ``None``, one ``Ellipsis`` and index arrays (lists, tuples, arrays, integer
+        tensors; a 2-D ``[P, N]`` array is N columns).  Index arrays must be contiguous in the key and of equal length P; they
+        become one ``[r_a, P, r_b]`` core.  An all-int key returns a 0-d tensor, every other key a ``Tensor``."""
+        from .indexing import getitem
+
+        return getitem(self, key)
+
+    def __setitem__(self, key, value):
+        _not_in_scope("assignment into a tensor train (__setitem__)")
+
     # ------------------------------------------------------------------ arithmetic used around the hot path
     def _scalar_like(self, value):
         c0 = self.cores[0]
