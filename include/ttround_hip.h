@@ -53,9 +53,9 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
-#define TTR_ABI_VERSION 12
+#define TTR_ABI_VERSION 13
 int ttr_version(void);
 const char* ttr_last_error(void);
 
@@ -700,6 +700,32 @@ int ttr_gather_chain(int dtype, int64_t nmodes, int64_t batch, int64_t P, const 
                      const int64_t* idx_strides, void* out, int64_t stride_ob, int64_t stride_or, int64_t stride_op,
                      int64_t stride_oc, int64_t direct_max_points, void* oob_flag, void* workspace, int64_t workspace_bytes,
                      void* stream);
+
+/*
+ * One gather step with a row map on its input (ABI 13; the interface update of TT-cross, cross.py:400-448):
+ *     Y[p, :] = X[xrow[p], :] @ G[:, idx[p], :]          p = 0 .. P-1
+ * X [rows_x, r] (row stride ldx, unit column stride), G [r, I, rn] at element strides gr, gi, gj, Y [P, rn] (row stride ldy).
+ * `xrow` (int64, device, may be NULL: X[p]) and `idx` (int64, device) are validated on the device: the int32 word at
+ * `oob_flag` is set to 1 when an entry is out of range (then nothing else is written), else 0.  The per-element FMA order is
+ * ttr_gather_chain's.  Ranks <= 512.  No workspace, no host synchronisation.
+ */
+int ttr_gather_step(int dtype, int64_t P, int64_t rows_x, int64_t r, int64_t rn, int64_t I, const void* X, int64_t ldx,
+                    const void* xrow, const void* G, int64_t gr, int64_t gi, int64_t gj, const void* idx, void* Y, int64_t ldy,
+                    void* oob_flag, void* stream);
+
+/*
+ * Maximum-volume rows (ABI 13; maxvol.py:115-170, py_maxvol with top_k_index = -1) of a batch of tall matrices
+ * A [batch, N, r] (row-major, item stride stride_ab), N > r, r <= 128:
+ *   index [batch, r] (int64, device): the chosen rows;  C [batch, N, r] (item stride stride_cb) = A A[index]^-1.
+ * Initial rows from LU with partial pivoting (getrf's pivots, ties to the first position), then Sherman-Morrison-Woodbury swaps
+ * while max |C| > tol (tol < 1 counts as 1) and fewer than max_iters swaps were made; the pivot of a swap is the first maximum
+ * of |C^T| in row-major order (the reference's divmod(abs(C).argmax(), N)).  C is solved fresh from the final rows.
+ * `status` (optional, device int32 [batch, 2]): done flag and number of swaps per item.  Every launch is independent of the host:
+ * nothing is read back.  Workspace: ttr_maxvol_workspace_bytes.  Items are independent: a batch gives bitwise the per-item result.
+ */
+int64_t ttr_maxvol_workspace_bytes(int dtype, int64_t N, int64_t r, int64_t batch);
+int ttr_maxvol(int dtype, int64_t batch, int64_t N, int64_t r, const void* A, int64_t stride_ab, double tol, int64_t max_iters,
+               void* index, void* C, int64_t stride_cb, void* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,8 @@
 ``import tntorch_amd as tn`` exposes the names of the reference (``tntorch/__init__.py:1-14``)
 that sit on the TT decomposition / rounding hot path: ``tn.Tensor``, ``tn.round_tt``,
 ``tn.round``, ``tn.truncated_svd``, the unfoldings, plus the small helpers the reference's
-tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``).
+tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``), and TT-cross (``tn.cross``, ``tn.maxvol``,
+``tn.meshgrid`` and the element-wise functions of ``ops``: ``tn.exp``, ``tn.cos``, ...).
 """
 
 from .tools import *  # noqa: F401,F403
@@ -12,6 +13,9 @@ from .tensor import *  # noqa: F401,F403
 from .create import *  # noqa: F401,F403
 from .metrics import *  # noqa: F401,F403
 from .matrix import *  # noqa: F401,F403
+from .maxvol import *  # noqa: F401,F403
+from .cross import *  # noqa: F401,F403
+from .ops import *  # noqa: F401,F403
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TTR_LIB_PATH") or os.path.join(_HERE, "libttround_hip.so")
 
 F32, F64 = 0, 1
-ABI_VERSION = 12  # include/ttround_hip.h: TTR_ABI_VERSION
+ABI_VERSION = 13  # include/ttround_hip.h: TTR_ABI_VERSION
 SCALE_NONE, SCALE_MUL, SCALE_DIV = 0, 1, 2
 EIG_RAW, EIG_REF, EIG_MATCH_DIAG = 0, 1, 2
 SOLVER_JACOBI_REL, SOLVER_JACOBI_ABS, SOLVER_TRIDIAG, SOLVER_JACOBI_LIVE = 0, 1, 2, 3  # `abs_floor` argument of ttr_eigh_trunc
@@ -190,6 +190,17 @@ _SIGNATURES = {
         c_int,
         [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
          c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
+    "ttr_gather_step": (
+        c_int,
+        [c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+         c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    ),
+    "ttr_maxvol_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64]),
+    "ttr_maxvol": (
+        c_int,
+        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int64, c_void_p],
     ),
     "ttr_debug_set_qr_stamps": (c_int, [c_void_p]),
     "ttr_debug_set_knob": (c_int, [c_int, c_int]),
@@ -1108,6 +1119,57 @@ def gather_chain(cores, idx, out: Optional[torch.Tensor] = None, direct_max_poin
     if int(flag.item()):  # the one host read of the call
         raise IndexError("index out of range: an index array entry lies outside its mode")
     return out
+
+
+@_on_device
+def gather_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tensor, idx: torch.Tensor,
+                out: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_gather_step: Y[p, :] = X[xrow[p], :] @ G[:, idx[p], :] for X [rows, r] (unit column stride), G [r, I, rn] (any
+    strides), int64 device vectors ``xrow`` (or None: X[p]) and ``idx`` of length P -> Y [P, rn].  Nothing is read back: an
+    out-of-range entry sets the device word ``flag`` (allocated when not given) and leaves Y unwritten."""
+    L = lib()
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 2 and G.dim() == 3 and X.dtype == G.dtype and X.shape[1] == G.shape[0]
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        X = X.contiguous()
+    P = idx.shape[0]
+    idx = idx.to(torch.int64).contiguous()
+    if xrow is not None:
+        xrow = xrow.to(torch.int64).contiguous()
+        assert xrow.shape[0] == P
+    r, I, rn = G.shape
+    if out is None:
+        out = torch.empty((P, rn), dtype=X.dtype, device=X.device)
+    assert tuple(out.shape) == (P, rn) and (rn == 1 or out.stride(1) == 1)
+    if flag is None:
+        flag = torch.empty(1, dtype=torch.int32, device=X.device)
+    ldx = int(X.stride(0)) if X.shape[0] > 1 else int(r)
+    ldy = int(out.stride(0)) if P > 1 else int(rn)
+    _check(L.ttr_gather_step(dt, P, X.shape[0], r, rn, I, X.data_ptr(), ldx, xrow.data_ptr() if xrow is not None else None,
+                             G.data_ptr(), *[int(s) for s in G.stride()], idx.data_ptr(), out.data_ptr(), ldy, flag.data_ptr(),
+                             _stream()), "ttr_gather_step")
+    return out
+
+
+@_on_device
+def maxvol(A: torch.Tensor, tol: float, max_iters: int, status: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ttr_maxvol on [B, N, r] (N > r): -> index [B, r] (int64), C [B, N, r] = A A[index]^-1.  ``status`` (int32 [B, 2], optional)
+    receives the done flag and the number of swaps per item."""
+    L = lib()
+    dt = dtype_code(A.dtype)
+    A = A.contiguous()
+    B, N, r = A.shape
+    index = torch.empty((B, r), dtype=torch.int64, device=A.device)
+    C = torch.empty((B, N, r), dtype=A.dtype, device=A.device)
+    wsb = L.ttr_maxvol_workspace_bytes(dt, N, r, B)
+    if wsb < 0:
+        raise ValueError("ttr_maxvol_workspace_bytes: bad arguments")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=A.device)
+    if status is not None:
+        assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2 * B
+    _check(L.ttr_maxvol(dt, B, N, r, A.data_ptr(), N * r, float(tol), int(max_iters), index.data_ptr(), C.data_ptr(), N * r,
+                        status.data_ptr() if status is not None else None, ws.data_ptr(), wsb, _stream()), "ttr_maxvol")
+    return index, C
 
 
 KNOB_QR_PANEL = 0

@@ -1826,3 +1826,13 @@ def mm(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
 def gather_chain(cores4: Sequence[torch.Tensor], idx: Sequence[torch.Tensor]) -> torch.Tensor:
     """Index-array block of tensor.py:1357-1378 (ttr_gather_chain): [B, r_0, P, r_N]; IndexError when an index is out of range."""
     return _hip.gather_chain(list(cores4), list(idx))
+
+
+def maxvol(A3: torch.Tensor, tol: float, max_iters: int):
+    """maxvol.py:115-170 (ttr_maxvol): index [B, r] int64, C [B, N, r] solved fresh from the final rows."""
+    return _hip.maxvol(A3, tol, max_iters)
+
+
+def gather_step(X: torch.Tensor, xrow, G: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """Y[p] = X[xrow[p]] @ G[:, idx[p], :] (ttr_gather_step; xrow None: X[p])."""
+    return _hip.gather_step(X, xrow, G, idx)

@@ -421,3 +421,32 @@ def gather_chain(cores4: Sequence[torch.Tensor], idx: Sequence[torch.Tensor]) ->
     for c, i in zip(cores4[1:], idx[1:]):
         X = torch.einsum("biaj,bjak->biak", X, c[:, :, i, :])
     return X
+
+
+def _maxvol_one(A: torch.Tensor, tol: float, max_iters: int):
+    N, r = A.shape
+    LU, piv = torch.linalg.lu_factor(A)  # getrf: the pivots of the reference's start (maxvol.py:138-145)
+    index = torch.arange(N)
+    for i, p in enumerate((piv[:r] - 1).tolist()):
+        index[[i, p]] = index[[p, i]]
+    U = torch.triu(LU[:r])
+    L11 = torch.tril(LU[:r], -1) + torch.eye(r, dtype=A.dtype)
+    C = torch.linalg.solve_triangular(U, A, upper=True, left=False)  # A = C L11 U
+    C = torch.linalg.solve_triangular(L11, C, upper=False, left=False, unitriangular=True)
+    iters = 0
+    while True:
+        q, p = divmod(int(torch.argmax(C.t().abs())), N)  # first maximum of |C^T| in row-major order
+        if not abs(float(C[p, q])) > tol or iters >= max_iters:
+            break
+        index[q] = p
+        x = C[p].clone()
+        x[q] -= 1.0
+        C.addr_(C[:, q] * (-1.0 / C[p, q]), x)  # C[n, k] += (alpha C[n, q]) x[k]
+        iters += 1
+    return index[:r].clone(), C
+
+
+def maxvol(A3: torch.Tensor, tol: float, max_iters: int):
+    """maxvol.py:115-170 on every item of [B, N, r] (N > r) -> index [B, r] int64, C [B, N, r]."""
+    out = [_maxvol_one(a, tol, max_iters) for a in A3]
+    return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])

@@ -150,13 +150,14 @@ __global__ void __launch_bounds__(kThreads) gather_kernel(const T* __restrict__ 
 // Y[row] = X[row] @ G[b][:, v, :] for the X rows of one tile (all with index value v): 64 rows x 64 columns per workgroup, k in
 // chunks of 32 through LDS, 4 x 4 outputs per thread.  Every output is fma(x[k], s[k][j], acc) for k = 0, 1, ..., r - 1.
 // direct: tile t covers rows [t_in_point * 64, ...) of point t / tiles_per_point, no permutation.
+// xmap (ttr_gather_step; NULL otherwise): point p reads X point xmap[p] instead of p.
 template <typename T>
 __global__ void __launch_bounds__(kThreads) step_kernel(const T* __restrict__ X, int64_t xb, int64_t xp, int64_t xi,
                                                         const T* __restrict__ G, int64_t gb, int64_t gr, int64_t gi, int64_t gj,
                                                         IdxCol c, int64_t P, int64_t I, int64_t ra, int64_t r, int64_t rn,
                                                         T* __restrict__ Y, int64_t yb, int64_t yp, int64_t yi, int64_t yj, int direct,
                                                         const int32_t* cnt, const int64_t* off, const int64_t* toff,
-                                                        const int64_t* perm, const int32_t* flag) {
+                                                        const int64_t* perm, const int32_t* flag, const int64_t* xmap) {
   __shared__ T xs[kTileK][kTileRows + 4];
   __shared__ T ss[kTileK][kTileCols + 4];
   __shared__ int64_t xrow[kTileRows], yrow[kTileRows];
@@ -192,7 +193,7 @@ __global__ void __launch_bounds__(kThreads) step_kernel(const T* __restrict__ X,
     if (row < rend) {
       int64_t q = row / ra, i = row % ra;
       int64_t p = direct ? q : perm[q];
-      xrow[tid] = b * xb + p * xp + i * xi;
+      xrow[tid] = b * xb + (xmap ? xmap[p] : p) * xp + i * xi;
       yrow[tid] = b * yb + p * yp + i * yi;
     } else {
       xrow[tid] = yrow[tid] = -1;
@@ -319,7 +320,7 @@ int gather_chain_impl(int64_t nmodes, int64_t batch, int64_t P, const int64_t* r
       }
       dim3 grid((unsigned)tiles, (unsigned)((rn + kTileCols - 1) / kTileCols), (unsigned)batch);
       hipLaunchKernelGGL(step_kernel<T>, grid, dim3(kThreads), 0, stream, X, xb, xp, xi, G, g[0], g[1], g[2], g[3], c, P, I, ra,
-                         r, rn, Y, yb, yp, yi, yj, direct ? 1 : 0, cnt, off, toff, perm, flag);
+                         r, rn, Y, yb, yp, yi, yj, direct ? 1 : 0, cnt, off, toff, perm, flag, (const int64_t*)nullptr);
     }
     X = Y;
     xb = yb;
@@ -380,4 +381,43 @@ extern "C" int ttr_gather_chain(int dtype, int64_t nmodes, int64_t batch, int64_
                                     (char*)workspace, L, s);
   return gather_chain_impl<double>(nmodes, batch, P, ranks, sizes, cores, core_strides, idx_dtype, idx, idx_strides, out, stride_ob,
                                    stride_or, stride_op, stride_oc, direct_max_points, (int32_t*)oob_flag, (char*)workspace, L, s);
+}
+
+// One step of the chain with a row map on its input (the interface update of TT-cross, cross.py:400-448):
+//   Y[p, :] = X[xrow[p], :] @ G[:, idx[p], :]      X [rows_x, r] (row stride ldx), G [r, I, rn] (strides gr, gi, gj), Y [P, rn]
+// xrow == NULL reads X[p].  Both index vectors (int64) are validated on the device first; out-of-range input sets *oob_flag and
+// writes nothing else.  The direct path of ttr_gather_chain (one tile per point), so no workspace and no host synchronisation.
+extern "C" int ttr_gather_step(int dtype, int64_t P, int64_t rows_x, int64_t r, int64_t rn, int64_t I, const void* X, int64_t ldx,
+                               const void* xrow, const void* G, int64_t gr, int64_t gi, int64_t gj, const void* idx, void* Y,
+                               int64_t ldy, void* oob_flag, void* stream) {
+  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_gather_step: bad dtype %d", dtype);
+  TTR_REQUIRE(P >= 0 && rows_x >= 1 && r >= 1 && rn >= 1 && I >= 1, TTR_E_INVALID, "ttr_gather_step: bad sizes");
+  TTR_REQUIRE(X && G && idx && oob_flag && (Y || P == 0), TTR_E_INVALID, "ttr_gather_step: NULL argument");
+  TTR_REQUIRE(I < ((int64_t)1 << 31) && rows_x < ((int64_t)1 << 31), TTR_E_UNSUPPORTED, "ttr_gather_step: sizes too large");
+  TTR_REQUIRE(r <= kMaxRank && rn <= kMaxRank, TTR_E_UNSUPPORTED, "ttr_gather_step: rank above %lld", (long long)kMaxRank);
+  TTR_REQUIRE(P < ((int64_t)1 << 31), TTR_E_UNSUPPORTED, "ttr_gather_step: too many points (%lld)", (long long)P);
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* flag = (int32_t*)oob_flag;
+  TTR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+  if (P == 0) return TTR_OK;
+  const unsigned pb = (unsigned)((P + kThreads - 1) / kThreads);
+  IdxCol c{idx, 1, 1};
+  hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, s, c, P, I, flag);
+  if (xrow) {
+    IdxCol cx{xrow, 1, 1};
+    hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, s, cx, P, rows_x, flag);
+  }
+  const dim3 grid((unsigned)P, (unsigned)((rn + kTileCols - 1) / kTileCols), 1);
+  if (dtype == TTR_F32)
+    hipLaunchKernelGGL(step_kernel<float>, grid, dim3(kThreads), 0, s, (const float*)X, (int64_t)0, ldx, (int64_t)0, (const float*)G,
+                       (int64_t)0, gr, gi, gj, c, P, I, (int64_t)1, r, rn, (float*)Y, (int64_t)0, ldy, (int64_t)0, (int64_t)1, 1,
+                       (const int32_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr, flag,
+                       (const int64_t*)xrow);
+  else
+    hipLaunchKernelGGL(step_kernel<double>, grid, dim3(kThreads), 0, s, (const double*)X, (int64_t)0, ldx, (int64_t)0,
+                       (const double*)G, (int64_t)0, gr, gi, gj, c, P, I, (int64_t)1, r, rn, (double*)Y, (int64_t)0, ldy, (int64_t)0,
+                       (int64_t)1, 1, (const int32_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                       (const int64_t*)nullptr, flag, (const int64_t*)xrow);
+  TTR_HIP_CHECK(hipGetLastError());
+  return TTR_OK;
 }

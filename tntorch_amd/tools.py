@@ -11,7 +11,36 @@ import time
 import numpy as np
 import torch
 
-__all__ = ["unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode"]
+__all__ = ["meshgrid", "unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode"]
+
+
+def meshgrid(*axes, batch=False):
+    """tools.py:135-166: N tensors of N dimensions (rank 1 each), the n-th varying along mode n.  Axes are ints (``arange``) or
+    vectors, cast to the default dtype; the cores live on the device of the first axis."""
+    from .tensor import Tensor
+
+    device = None
+    if not hasattr(axes, "__len__"):
+        axes = [axes]
+    if hasattr(axes[0], "__len__"):
+        axes = axes[0]
+    if hasattr(axes[0], "device"):
+        device = axes[0].device
+    axes = list(axes)
+    N = len(axes)
+    for n in range(N):
+        if not hasattr(axes[n], "__len__"):
+            axes[n] = torch.arange(axes[n], dtype=torch.get_default_dtype())
+    tensors = []
+    for n in range(N):
+        cores = [torch.ones(1, len(ax), 1).to(device) for ax in axes]
+        if isinstance(axes[n], torch.Tensor):
+            cores[n] = axes[n].type(torch.get_default_dtype())
+        else:
+            cores[n] = torch.tensor(np.asarray(axes[n]), dtype=torch.get_default_dtype())
+        cores[n] = cores[n][None, :, None].to(device)
+        tensors.append(Tensor(cores, device=device, batch=batch))
+    return tensors
 
 
 def unfolding(data: torch.Tensor, n: int, batch: bool = False) -> torch.Tensor:
