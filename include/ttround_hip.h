@@ -706,7 +706,8 @@ int ttr_gather_chain(int dtype, int64_t nmodes, int64_t batch, int64_t P, const 
  *     Y[p, :] = X[xrow[p], :] @ G[:, idx[p], :]          p = 0 .. P-1
  * X [rows_x, r] (row stride ldx, unit column stride), G [r, I, rn] at element strides gr, gi, gj, Y [P, rn] (row stride ldy).
  * `xrow` (int64, device, may be NULL: X[p]) and `idx` (int64, device) are validated on the device: the int32 word at
- * `oob_flag` is set to 1 when an entry is out of range (then nothing else is written), else 0.  The per-element FMA order is
+ * `oob_flag` is set to 1 when an entry is out of range (then nothing else is written), else 0.  `idx` may be negative
+ * (-I <= idx < I, wrapped as in torch); `xrow` may not (0 <= xrow < rows_x).  The per-element FMA order is
  * ttr_gather_chain's.  Ranks <= 512.  No workspace, no host synchronisation.
  */
 int ttr_gather_step(int dtype, int64_t P, int64_t rows_x, int64_t r, int64_t rn, int64_t I, const void* X, int64_t ldx,

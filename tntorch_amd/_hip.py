@@ -1125,8 +1125,9 @@ def gather_chain(cores, idx, out: Optional[torch.Tensor] = None, direct_max_poin
 def gather_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tensor, idx: torch.Tensor,
                 out: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ttr_gather_step: Y[p, :] = X[xrow[p], :] @ G[:, idx[p], :] for X [rows, r] (unit column stride), G [r, I, rn] (any
-    strides), int64 device vectors ``xrow`` (or None: X[p]) and ``idx`` of length P -> Y [P, rn].  Nothing is read back: an
-    out-of-range entry sets the device word ``flag`` (allocated when not given) and leaves Y unwritten."""
+    strides), int64 device vectors ``xrow`` (or None: X[p]) and ``idx`` of length P -> Y [P, rn].  ``idx`` wraps negative values
+    (-I <= idx < I); ``xrow`` does not (0 <= xrow < rows).  Nothing is read back: an out-of-range entry sets the device word
+    ``flag`` (allocated when not given) and leaves Y unwritten."""
     L = lib()
     dt = dtype_code(X.dtype)
     assert X.dim() == 2 and G.dim() == 3 and X.dtype == G.dtype and X.shape[1] == G.shape[0]

@@ -28,6 +28,8 @@ import torch
 
 __all__ = ["cross"]
 
+MAX_DEVICE_RANK = 128  # ttr_maxvol's limit (r x r inverse in LDS): device cores take no larger bond
+
 
 # ------------------------------------------------------------------------------------------------ host path (reference ops)
 def _init_interfaces_host(tensors, rsets, N, device, dtype):
@@ -203,6 +205,9 @@ def cross(
     Rs = np.array(ranks_tt)
     for n in list(range(1, N)) + list(range(N - 1, -1, -1)):
         Rs[n] = min(Rs[n - 1] * Is[n - 1], Rs[n], Is[n] * Rs[n + 1])
+    if on_dev and max(Rs) > MAX_DEVICE_RANK:  # before the function is first called
+        raise NotImplementedError(
+            "cross: ranks above {} are not supported on the device (capped ranks {})".format(MAX_DEVICE_RANK, Rs.tolist()))
 
     # Random draws in the reference's order: initial cores, right sets, validation set (cross.py:282-300)
     cores = [torch.randn(Rs[n], Is[n], Rs[n + 1]) for n in range(N)]
@@ -366,6 +371,9 @@ def cross(
             newRs[1:-1] = np.minimum(rmax, newRs[1:-1] + kickrank)
             for n in list(range(1, N)) + list(range(N - 1, 0, -1)):
                 newRs[n] = min(newRs[n - 1] * Is[n - 1], newRs[n], Is[n] * newRs[n + 1])
+            if on_dev and max(newRs) > MAX_DEVICE_RANK:
+                raise NotImplementedError(
+                    "cross: rank growth to {} exceeds the device limit of {} (lower rmax)".format(max(newRs), MAX_DEVICE_RANK))
             extra = np.hstack(
                 [np.random.randint(0, Is[n + 1], [max(newRs), 1]) for n in range(N - 1)] + [np.zeros([max(newRs), 1], dtype=int)]
             )

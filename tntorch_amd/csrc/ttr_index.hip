@@ -34,16 +34,16 @@ __device__ __forceinline__ int64_t load_idx(const IdxCol& c, int64_t q) {
   return c.is64 ? ((const int64_t*)c.p)[q * c.stride] : (int64_t)((const int32_t*)c.p)[q * c.stride];
 }
 
-// wrapped index of point q, or -1 when out of range
-__device__ __forceinline__ int64_t idx_value(const IdxCol& c, int64_t q, int64_t I) {
+// wrapped index of point q, or -1 when out of range; wrap == 0: negative values are out of range too (row maps)
+__device__ __forceinline__ int64_t idx_value(const IdxCol& c, int64_t q, int64_t I, int wrap = 1) {
   int64_t v = load_idx(c, q);
-  if (v < 0) v += I;
+  if (v < 0 && wrap) v += I;
   return (v < 0 || v >= I) ? -1 : v;
 }
 
-__global__ void __launch_bounds__(kThreads) validate_kernel(IdxCol c, int64_t P, int64_t I, int32_t* flag) {
+__global__ void __launch_bounds__(kThreads) validate_kernel(IdxCol c, int64_t P, int64_t I, int32_t* flag, int wrap) {
   int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  bool bad = q < P && idx_value(c, q, I) < 0;
+  bool bad = q < P && idx_value(c, q, I, wrap) < 0;
   if (__any(bad) && (threadIdx.x & (kWave - 1)) == 0) atomicOr(flag, 1);
 }
 
@@ -281,7 +281,7 @@ int gather_chain_impl(int64_t nmodes, int64_t batch, int64_t P, const int64_t* r
   const unsigned pb = (unsigned)((P + kThreads - 1) / kThreads);
   for (int64_t n = 0; n < nmodes; ++n) {
     IdxCol c{idx[n], idx_strides[n], idx_dtype};
-    hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, stream, c, P, sizes[n], flag);
+    hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, stream, c, P, sizes[n], flag, 1);
   }
   const bool direct = P <= (direct_max < 0 ? kDefaultDirectMax : direct_max);
   const int64_t ra = ranks[0];
@@ -385,14 +385,14 @@ extern "C" int ttr_gather_chain(int dtype, int64_t nmodes, int64_t batch, int64_
 
 // One step of the chain with a row map on its input (the interface update of TT-cross, cross.py:400-448):
 //   Y[p, :] = X[xrow[p], :] @ G[:, idx[p], :]      X [rows_x, r] (row stride ldx), G [r, I, rn] (strides gr, gi, gj), Y [P, rn]
-// xrow == NULL reads X[p].  Both index vectors (int64) are validated on the device first; out-of-range input sets *oob_flag and
-// writes nothing else.  The direct path of ttr_gather_chain (one tile per point), so no workspace and no host synchronisation.
+// xrow == NULL reads X[p].  Both index vectors (int64) are validated on the device first (idx wraps negative values as in
+// torch, xrow does not: a row map entry must be in 0 .. rows_x-1); out-of-range input sets *oob_flag and writes nothing else.  The direct path of ttr_gather_chain (one tile per point), so no workspace and no host synchronisation.
 extern "C" int ttr_gather_step(int dtype, int64_t P, int64_t rows_x, int64_t r, int64_t rn, int64_t I, const void* X, int64_t ldx,
                                const void* xrow, const void* G, int64_t gr, int64_t gi, int64_t gj, const void* idx, void* Y,
                                int64_t ldy, void* oob_flag, void* stream) {
   TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_gather_step: bad dtype %d", dtype);
   TTR_REQUIRE(P >= 0 && rows_x >= 1 && r >= 1 && rn >= 1 && I >= 1, TTR_E_INVALID, "ttr_gather_step: bad sizes");
-  TTR_REQUIRE(X && G && idx && oob_flag && (Y || P == 0), TTR_E_INVALID, "ttr_gather_step: NULL argument");
+  TTR_REQUIRE(X && G && oob_flag && ((idx && Y) || P == 0), TTR_E_INVALID, "ttr_gather_step: NULL argument");
   TTR_REQUIRE(I < ((int64_t)1 << 31) && rows_x < ((int64_t)1 << 31), TTR_E_UNSUPPORTED, "ttr_gather_step: sizes too large");
   TTR_REQUIRE(r <= kMaxRank && rn <= kMaxRank, TTR_E_UNSUPPORTED, "ttr_gather_step: rank above %lld", (long long)kMaxRank);
   TTR_REQUIRE(P < ((int64_t)1 << 31), TTR_E_UNSUPPORTED, "ttr_gather_step: too many points (%lld)", (long long)P);
@@ -402,10 +402,10 @@ extern "C" int ttr_gather_step(int dtype, int64_t P, int64_t rows_x, int64_t r, 
   if (P == 0) return TTR_OK;
   const unsigned pb = (unsigned)((P + kThreads - 1) / kThreads);
   IdxCol c{idx, 1, 1};
-  hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, s, c, P, I, flag);
+  hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, s, c, P, I, flag, 1);
   if (xrow) {
     IdxCol cx{xrow, 1, 1};
-    hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, s, cx, P, rows_x, flag);
+    hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, s, cx, P, rows_x, flag, 0);  // no wrap: rows 0 .. rows_x-1
   }
   const dim3 grid((unsigned)P, (unsigned)((rn + kTileCols - 1) / kTileCols), 1);
   if (dtype == TTR_F32)
