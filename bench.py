@@ -10,8 +10,13 @@ gathers the rounded cores on rank 0 with a single RCCL gather.
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full   # + roofline, parity, extras, configs, CPU baseline
     python bench.py --config c3        # BASELINE config C3 (512 dense 32^5 -> rank 8), one line in the same format
     python bench.py --config c1        # BASELINE config C1 class (dense 64^k -> rank 16, the largest k that fits)
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  Everything that
+takes runs of its own -- the per-kernel roofline pass, the parity check against the oracle, the small-batch / B = 2048 /
+decaying-spectrum extras, BASELINE's other configs, the CPU baseline, the N > 1 gather-alone timing -- runs with --full.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the definition of every field).
 """
@@ -389,19 +394,21 @@ def _pick(d, keys, nd=4):
     return {k: v for k, v in out.items() if v is not None}   # (NaN / Infinity round to None: dropped, never printed)
 
 
-def compact_line(res):
+def compact_line(res, sidecar=True):
     """The ONE line bench.py prints (contract fields + `roofline` + `cpu_baseline` + one-number summaries); everything else
     -- `configs`, `extras`, `roofline_per_kernel`, per-step records -- goes to the sidecar ``FULL_SIDECAR`` and to stderr.
+    A plain run's result has no `roofline` (no per-kernel pass) and writes no sidecar (``sidecar=False``): neither is named.
     tests/test_bench_cpu.py pins ``len(line) < LINE_LIMIT`` and the fields the driver checks."""
     out = {k: res.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                    "scaling", "vs_baseline", "dtype", "data")}
     out["value"], out["ms_per_step"] = _r(out["value"], 7), _r(out["ms_per_step"], 6)
     out["config"] = _pick(res.get("config", {}), ("workload", "tensors_per_gpu_per_step", "algorithm", "streams_per_gpu", "parallelism"))
-    ro = res.get("roofline") or {}
-    out["roofline"] = _pick(ro, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "frac_mfma_executed",
-                                 "frac_hbm_executed", "frac_algorithmic", "executed_share_of_algorithmic_flops", "frac_hbm_traffic",
-                                 "mfma_util", "avg_launch_ms", "launches", "input_aware"))
-    out["roofline"].setdefault("traffic", None)
+    ro = res.get("roofline")
+    if ro is not None:
+        out["roofline"] = _pick(ro, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "frac_mfma_executed",
+                                     "frac_hbm_executed", "frac_algorithmic", "executed_share_of_algorithmic_flops", "frac_hbm_traffic",
+                                     "mfma_util", "avg_launch_ms", "launches", "input_aware"))
+        out["roofline"].setdefault("traffic", None)
     cb = res.get("cpu_baseline")
     if cb:
         out["cpu_baseline"] = _pick(cb, ("value", "unit", "cores", "kind", "algorithm", "reference_factor"))
@@ -463,7 +470,8 @@ def compact_line(res):
         cf[k] = e
     if cf:
         out["configs"] = cf
-    out["full"] = FULL_SIDECAR
+    if sidecar:
+        out["full"] = FULL_SIDECAR
     line = json.dumps(out, allow_nan=False)
     # (belt and braces: a line above the limit loses its optional blocks, never its contract fields)
     for drop in ("kinds", "kernel_ms_per_step", "sweep_roofline", "extras", "configs", "gather", "sweep"):
@@ -488,6 +496,14 @@ def emit(res):
     print("bench.py full result: " + full, file=sys.stderr)
     sys.stderr.flush()
     print(compact_line(res))
+    sys.stdout.flush()
+
+
+def emit_plain(res):
+    """A plain run: the result object -> stderr, the compact line -> stdout (the LAST line, flushed); no sidecar is written."""
+    print("bench.py result: " + json.dumps(res, default=str), file=sys.stderr)
+    sys.stderr.flush()
+    print(compact_line(res, sidecar=False))
     sys.stdout.flush()
 
 
@@ -549,14 +565,18 @@ def main():
                     help="tensors per GPU per step (4096: 26 GB of resident cores, ~90 GB with workspaces and two steps in flight; round 5 -- "
                          "rounds 1-4 ran 2048, still reported as `extras.batch_2048`: the launches' tails amortise better, +6 %%)")
     ap.add_argument("--algorithm", default="svd", choices=["svd", "eig"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-kernel roofline pass, the parity check against the oracle, `extras`, `configs`, "
+                         "the CPU baseline and (N > 1) the `gather` block, each in runs of its own after the timed steps; the full "
+                         "result object goes to " + FULL_SIDECAR + ".  Without it a run times the steps and prints the line, nothing else")
     ap.add_argument("--config", default="metric", choices=["metric", "c1", "c2", "c3", "c4"],
-                    help="metric (default): the headline workload (its line also carries `configs`: one entry per BASELINE config); "
+                    help="metric (default): the headline workload (with --full its line also carries `configs`: one entry per BASELINE config); "
                          "c1 .. c4: one of BASELINE's other configs alone (tools/bench_configs.py)")
     ap.add_argument("--variant", default="randn", choices=["randn", "lowrank"],
                     help="--config c1 | c3: the input of SURVEY 8d (plain randn, or TT rank = the cap of unit RMS + 1e-3 randn)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the small-batch / single-tensor extra measurements")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C1 .. C4 entries of the default line (`configs`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the small-batch / single-tensor extra measurements")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the C1 .. C4 entries of the line (`configs`)")
     ap.add_argument("--gather", default=os.environ.get("TTR_BENCH_GATHER", "end"), choices=["end", "step", "none"],
                     help="N > 1: `end` (default; north_star: 'a single RCCL gather over xGMI at the end') = ONE gather of the last "
                          "step's rounded cores after the last timed step, inside the timed region; `step` = every step's result is "
@@ -684,9 +704,9 @@ def main():
             assert torch.isfinite(gathered[-1].cores[3]).all()
 
     # ---- N > 1: the gather of one step's result ALONE (nothing else running), so that a scaling line shows which side
-    # binds: `gather.alone_ms` against `ms_per_step`.  Every peer sends its packed cores over its own xGMI link to rank 0.
+    # binds: `gather.alone_ms` against `ms_per_step`.  Every peer sends its packed cores over its own xGMI link to rank 0.  --full only.
     gather_info = None
-    if dist_on:
+    if dist_on and args.full:
         per_peer = sum(c.numel() * c.element_size() for c in out.cores)
         fence()
         g0 = time.perf_counter()
@@ -724,32 +744,30 @@ def main():
 
     # ---- per-kernel device time over an identical pass (HIP events on the launch stream).  The timed region
     # above runs sub-batches on several streams so that kernels overlap; here every kernel must run alone for
-    # its duration to mean anything, so the same work is issued on ONE stream.
-    _hipops.STREAM_CHUNKS_ENABLED = False
-    # (one untimed step first: this is the first time these kernels run on THIS stream's queue -- the runtime sizes a queue's
-    # scratch memory when a kernel first needs it there, a one-off stall of tens of milliseconds that landed in the `eigh` kind of
-    # some runs: 8.1 instead of 1.5 ms/step averaged over 20 steps, with the timed region of the same process at 13.7 ms/step)
-    t = tn.Tensor(inp, batch=True)
-    t.round_tt(rmax=R_OUT, algorithm=args.algorithm)
-    torch.cuda.synchronize()
-    _hip.prof_enable(2)   # per-kind device times + the executed-work census (include/ttround_hip.h: ttr_prof_collect_work)
-    for _ in range(args.steps):
+    # its duration to mean anything, so the same work is issued on ONE stream.  --full only.
+    if args.full:
+        _hipops.STREAM_CHUNKS_ENABLED = False
+        # (one untimed step first: this is the first time these kernels run on THIS stream's queue -- the runtime sizes a queue's
+        # scratch memory when a kernel first needs it there, a one-off stall of tens of milliseconds that landed in the `eigh` kind of
+        # some runs: 8.1 instead of 1.5 ms/step averaged over 20 steps, with the timed region of the same process at 13.7 ms/step)
         t = tn.Tensor(inp, batch=True)
         t.round_tt(rmax=R_OUT, algorithm=args.algorithm)
-    torch.cuda.synchronize()
-    prof = _hip.prof_collect()
-    work = _hip.prof_collect_work()
-    _hip.prof_enable(False)
-    _hipops.STREAM_CHUNKS_ENABLED = not args.single_stream
+        torch.cuda.synchronize()
+        _hip.prof_enable(2)   # per-kind device times + the executed-work census (include/ttround_hip.h: ttr_prof_collect_work)
+        for _ in range(args.steps):
+            t = tn.Tensor(inp, batch=True)
+            t.round_tt(rmax=R_OUT, algorithm=args.algorithm)
+        torch.cuda.synchronize()
+        prof = _hip.prof_collect()
+        work = _hip.prof_collect_work()
+        _hip.prof_enable(False)
+        _hipops.STREAM_CHUNKS_ENABLED = not args.single_stream
 
     if rank == 0:
         assert list(out.ranks_tt) == [1] + [R_OUT] * (N_CORES - 1) + [1], out.ranks_tt
         tensors = B * world * args.steps
         ms_per_step = elapsed / args.steps * 1e3
         cores_per_s = tensors * N_CORES / elapsed
-        pmc, pmc_note = load_pmc()
-        per_kind = per_kind_roofline(prof, work, B, args.steps, pmc)
-        dom = max(per_kind, key=lambda k: per_kind[k]["ms_per_step"])
         res = {
             "metric": f"TT rounding 64^8 rank-64 -> rank-32 (round_tt rmax=32), cores/s, resident batch of {B} trains per GPU",
             "value": cores_per_s,
@@ -782,7 +800,6 @@ def main():
                 "flat_spectrum": "kept singular values within a factor 8: pass 2 skipped, pass 1 by the top-r solver",
             },
             "nccl_ranks": nccl_ranks,
-            "gather": gather_info,
             "allocator": getattr(timed_steps, "allocator", None),
             # device time between the completion events of consecutive steps (warm-up steps included, first one omitted)
             "host_enqueue_ms": host_ms,
@@ -791,11 +808,20 @@ def main():
             "gflops": FLOP_PER_TENSOR * tensors / elapsed / 1e9,
             "whole_sweep_frac_of_mfma_f32_peak": FLOP_PER_TENSOR * tensors / elapsed / 1e12 / MFMA_F32_PEAK_TF,
             "whole_sweep_hbm_frac": BYTES_PER_TENSOR * tensors / elapsed / 1e9 / HBM_PEAK_GBS,
+        }
+        if not args.full:
+            emit_plain(res)
+    if rank == 0 and args.full:
+        pmc, pmc_note = load_pmc()
+        per_kind = per_kind_roofline(prof, work, B, args.steps, pmc)
+        dom = max(per_kind, key=lambda k: per_kind[k]["ms_per_step"])
+        res.update({
+            "gather": gather_info,
             "whole_sweep_executed": sweep_executed(per_kind, ms_per_step),
             "roofline": headline_roofline(per_kind, dom, prof, args.steps, pmc_note),
             "roofline_per_kernel": per_kind,
             "kernel_ms_per_step": {k: v["ms"] / args.steps for k, v in prof.items() if v["launches"] > 0},
-        }
+        })
         try:
             res["parity"] = parity_check(inp, out, (0, B - 1) if B > 1 else (0,))
         except Exception as e:  # noqa: BLE001

@@ -143,3 +143,23 @@ def test_steps_must_be_positive(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
     with pytest.raises(SystemExit):
         bench.main()
+
+
+def test_plain_line_names_no_full_only_block(tmp_path, capsys, monkeypatch):
+    """A plain run (no --full) has no per-kernel pass, parity check, extras, configs or CPU baseline: its line carries the
+    contract fields and nothing that would need them, and it writes no sidecar."""
+    full = _stub_full_result()
+    res = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                "vs_baseline", "dtype", "data", "config", "nccl_ranks", "tensors_per_s", "gflops")}
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    (tmp_path / "profiles").mkdir()
+    bench.emit_plain(res)
+    cap = capsys.readouterr()
+    out_lines = [x for x in cap.out.splitlines() if x.strip()]
+    assert len(out_lines) == 1 and len(out_lines[0]) < bench.LINE_LIMIT
+    d = json.loads(out_lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert d[k] == (bench._r(res[k], 7) if k == "value" else bench._r(res[k], 6) if k == "ms_per_step" else res[k]), k
+    for k in ("roofline", "cpu_baseline", "parity", "extras", "configs", "gather", "kinds", "full"):
+        assert k not in d, k
+    assert list((tmp_path / "profiles").iterdir()) == [] and "bench.py result" in cap.err

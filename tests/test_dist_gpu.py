@@ -1,7 +1,7 @@
 """Multi-GPU path on real devices: two ranks over `nccl` (= RCCL over xGMI on ROCm), one process per GPU, shard a
 batch, round their shard with no communication and gather the packed cores once (plain and pipelined form); the
 result equals the single-process rounding bit for bit.  Needs two visible GPUs (skipped on the 1-GPU test box), plus
-`bench.py` under `torch.distributed.run --nproc-per-node 1` (the driver's launch form) on one GPU."""
+`bench.py` under `torch.distributed.run --nproc-per-node 1` (the driver's launch form) on one GPU, and its plain run."""
 import json
 import os
 import socket
@@ -91,7 +91,7 @@ def test_bench_under_torchrun_single_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "130", "--no-cpu-baseline", "--no-extras"]
+           "--batch", "130", "--full", "--no-cpu-baseline", "--no-extras"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -100,6 +100,24 @@ def test_bench_under_torchrun_single_rank():
     assert d["parity"]["ok"], d["parity"]
     # at this small batch the latency-bound eigensolver can be the dominant kind: bench.py labels it "valu"
     assert d["roofline"]["bound"] in ("mfma", "hbm", "valu") and 0 < d["roofline"]["frac"] < 1
+
+
+def test_bench_plain_run(tmp_path):
+    """`python bench.py --gpus 1` without --full: the timed steps, --dump-outputs and the line, nothing else -- no parity,
+    roofline, extras, configs or CPU baseline in the line, no sidecar written (small batch: a launch-path test, not a timing)."""
+    sidecar = os.path.join(ROOT, "profiles", "bench_full_latest.json")
+    before = os.stat(sidecar).st_mtime_ns if os.path.exists(sidecar) else None
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "130",
+           "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "cores/s" and d["value"] > 0
+    assert d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    for k in ("roofline", "parity", "cpu_baseline", "extras", "configs", "gather", "full"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path / "out")) == [f"core{k}.npy" for k in range(8)]
+    assert (os.stat(sidecar).st_mtime_ns if os.path.exists(sidecar) else None) == before
 
 
 def _nccl1_worker(port, q):
@@ -170,7 +188,7 @@ def test_bench_forced_dist_single_rank(mode):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TTR_BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-           "--batch", "130", "--no-cpu-baseline", "--no-extras", "--gather", mode]
+           "--batch", "130", "--full", "--no-cpu-baseline", "--no-extras", "--gather", mode]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,6 +1,6 @@
 """BASELINE.json's non-headline configs (C1 .. C4) measured through the public API on ONE GPU, for `bench.py`:
 
-    python bench.py                      # default run: the metric line carries `configs` = one entry per config below
+    python bench.py --full               # full run: the metric line carries `configs` = one entry per config below
     python bench.py --config c2          # (c1 | c2 | c3 | c4) one config alone, one JSON line
 
 Every entry has: `workload`, `ms` (median of the timed repetitions), the ALGORITHMIC flops / bytes of SURVEY.md section

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B=2048
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $R/bench.py --steps 5 --warmup 2 --single-stream --no-cpu-baseline --no-extras > $OUT/kt_bench.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $R/bench.py --steps 5 --warmup 2 --full --single-stream --no-cpu-baseline --no-extras > $OUT/kt_bench.json 2> $OUT/kt.err
 python $R/tools/rocprof_summary.py $(find $OUT/kt -name "*kernel_trace.csv" | head -1) > $OUT/kernel_stats.txt 2>> $OUT/kt.err
 for spec in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "mfma:SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32"; do
   name=${spec%%:*}; ctrs=${spec#*:}
