@@ -53,9 +53,9 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
-#define TTR_ABI_VERSION 13
+#define TTR_ABI_VERSION 14
 int ttr_version(void);
 const char* ttr_last_error(void);
 
@@ -727,6 +727,44 @@ int ttr_gather_step(int dtype, int64_t P, int64_t rows_x, int64_t r, int64_t rn,
 int64_t ttr_maxvol_workspace_bytes(int dtype, int64_t N, int64_t r, int64_t batch);
 int ttr_maxvol(int dtype, int64_t batch, int64_t N, int64_t r, const void* A, int64_t stride_ab, double tol, int64_t max_iters,
                void* index, void* C, int64_t stride_cb, void* status, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * TT completion by ALS (ABI 14; interpolation.py:9-119, `optimize_core`): the per-slice least-squares update of core mu, ranks
+ * r0 x r1, K = r0 r1 <= 1024.  A sample p of slice i contributes the Khatri-Rao row k_p = L_p (x) R_p, k_p[a r1 + b] = L_p[a] R_p[b]
+ * (L [P, r0] the left interfaces, R [P, r1] the right ones, both row-major with leading dimensions ldl / ldr), so the solution
+ * x_i reshapes directly to core[:, i, :].  (The reference orders its design columns (b, a) and reshapes them as (a, b): its cores
+ * with two ranks > 1 come out scrambled.  These entries compute the true minimiser.)
+ *
+ * ttr_als_normal replaces the per-slice `torch.where` / Khatri-Rao product / lstsq of the reference with the normal equations,
+ * accumulated per TASK t (a run perm[task_begin[t] .. task_end[t]) of the samples of one slice; the caller splits long slices
+ * into several tasks, so skewed data does not serialise on one workgroup):
+ *   Gp[t] (K x K, contiguous) = sum_p w_p^2 k_p k_p^T,   hp[t] (K) = sum_p w_p^2 y_p k_p      (w NULL: w_p = 1)
+ * on v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 (true fp64 / fp32 inputs), the rows k_p formed in registers from LDS-staged
+ * L / R rows: the P x K design matrix is never stored.  The lower-triangle 16 x 16 tiles are spread over
+ * ttr_als_normal_groups(r0, r1) workgroups per task; Gp is written exactly symmetric.  An empty task writes zeros.
+ * No workspace, no host synchronisation.
+ */
+int64_t ttr_als_normal_groups(int64_t r0, int64_t r1);
+int ttr_als_normal(int dtype, int64_t ntasks, int64_t r0, int64_t r1, const void* L, int64_t ldl, const void* R, int64_t ldr,
+                   const void* w, const void* y, const void* perm, const void* task_begin, const void* task_end, void* Gp,
+                   void* hp, void* stream);
+/*
+ * Batched SPD solve of the summed systems (replaces the reference's per-slice lstsq): item i (0 <= i < n_items) is the sum of
+ * the partials Gp / hp [part_off[i] - part_base, part_off[i + 1] - part_base) (part_off: int64, device).  One workgroup per item,
+ * right-looking Cholesky out of LDS when (K^2 + K) elements fit in 60 KiB, else in place in Gsum / hsum (global memory).
+ * status[i] (int32) = 1: solved, x_i written to X[i s_item + (k / inner) s_a + (k % inner) s_b], k = 0 .. K-1;
+ *                   = 0: a pivot fell to K eps max(diag G_i) or below, or counts[i] < K (`counts`, optional int64 [n_items]:
+ *                     the item's number of samples -- fewer than K make it singular whatever the rounding).  X is
+ *                     not written; Gsum[i] (K x K) / hsum[i] (K) receive the summed system for the minimum-norm fallback:
+ *                     ttr_eigh_trunc(Gsum, TTR_EIG_RAW, skip_items = status, Jacobi), t = V^T hsum (ttr_gemm), then
+ * ttr_pinv_finish: for the items with status 0, x_i = V diag(lambda+) t with lambda = sigma^2, lambda+ = 1 / lambda above
+ * K eps lambda_max and 0 at or below it (gelsd's minimum-norm solution of the normal equations).  No host synchronisation.
+ */
+int ttr_spd_solve(int dtype, int64_t n_items, int64_t K, const void* Gp, const void* hp, const void* part_off, int64_t part_base,
+                  void* X, int64_t inner, int64_t s_item, int64_t s_a, int64_t s_b, void* Gsum, void* hsum, void* status,
+                  const void* counts, void* stream);
+int ttr_pinv_finish(int dtype, int64_t n_items, int64_t K, const void* V, const void* sigma, const void* t, const void* status,
+                    void* X, int64_t inner, int64_t s_item, int64_t s_a, int64_t s_b, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@
 that sit on the TT decomposition / rounding hot path: ``tn.Tensor``, ``tn.round_tt``,
 ``tn.round``, ``tn.truncated_svd``, the unfoldings, plus the small helpers the reference's
 tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``), and TT-cross (``tn.cross``, ``tn.maxvol``,
-``tn.meshgrid`` and the element-wise functions of ``ops``: ``tn.exp``, ``tn.cos``, ...).
+``tn.meshgrid`` and the element-wise functions of ``ops``: ``tn.exp``, ``tn.cos``, ...), and TT completion from samples
+(``tn.als_completion``).
 """
 
 from .tools import *  # noqa: F401,F403
@@ -16,6 +17,7 @@ from .matrix import *  # noqa: F401,F403
 from .maxvol import *  # noqa: F401,F403
 from .cross import *  # noqa: F401,F403
 from .ops import *  # noqa: F401,F403
+from .interpolation import *  # noqa: F401,F403
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

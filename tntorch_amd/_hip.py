@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TTR_LIB_PATH") or os.path.join(_HERE, "libttround_hip.so")
 
 F32, F64 = 0, 1
-ABI_VERSION = 13  # include/ttround_hip.h: TTR_ABI_VERSION
+ABI_VERSION = 14  # include/ttround_hip.h: TTR_ABI_VERSION
 SCALE_NONE, SCALE_MUL, SCALE_DIV = 0, 1, 2
 EIG_RAW, EIG_REF, EIG_MATCH_DIAG = 0, 1, 2
 SOLVER_JACOBI_REL, SOLVER_JACOBI_ABS, SOLVER_TRIDIAG, SOLVER_JACOBI_LIVE = 0, 1, 2, 3  # `abs_floor` argument of ttr_eigh_trunc
@@ -201,6 +201,21 @@ _SIGNATURES = {
         c_int,
         [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
          c_int64, c_void_p],
+    ),
+    "ttr_als_normal_groups": (c_int64, [c_int64, c_int64]),
+    "ttr_als_normal": (
+        c_int,
+        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "ttr_spd_solve": (
+        c_int,
+        [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "ttr_pinv_finish": (
+        c_int,
+        [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p],
     ),
     "ttr_debug_set_qr_stamps": (c_int, [c_void_p]),
     "ttr_debug_set_knob": (c_int, [c_int, c_int]),
@@ -1171,6 +1186,74 @@ def maxvol(A: torch.Tensor, tol: float, max_iters: int, status: Optional[torch.T
     _check(L.ttr_maxvol(dt, B, N, r, A.data_ptr(), N * r, float(tol), int(max_iters), index.data_ptr(), C.data_ptr(), N * r,
                         status.data_ptr() if status is not None else None, ws.data_ptr(), wsb, _stream()), "ttr_maxvol")
     return index, C
+
+
+
+def als_normal_groups(r0: int, r1: int) -> int:
+    return int(lib().ttr_als_normal_groups(int(r0), int(r1)))
+
+
+@_on_device
+def als_normal(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: torch.Tensor, perm: torch.Tensor,
+               task_begin: torch.Tensor, task_end: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ttr_als_normal: per task t, Gp[t] = sum w_p^2 k_p k_p^T [K, K] and hp[t] = sum w_p^2 y_p k_p [K] over the samples
+    perm[task_begin[t]:task_end[t]], k_p = L[p] (x) R[p] (L [P, r0], R [P, r1]); returns (Gp [T, K, K], hp [T, K])."""
+    dt = dtype_code(L.dtype)
+    assert L.dim() == 2 and R.dim() == 2 and L.dtype == R.dtype == y.dtype and L.shape[0] == R.shape[0]
+    if L.shape[1] > 1 and L.stride(1) != 1:
+        L = L.contiguous()
+    if R.shape[1] > 1 and R.stride(1) != 1:
+        R = R.contiguous()
+    r0, r1 = int(L.shape[1]), int(R.shape[1])
+    ldl = int(L.stride(0)) if L.shape[0] > 1 else r0
+    ldr = int(R.stride(0)) if R.shape[0] > 1 else r1
+    y = y.contiguous()
+    if w is not None:
+        assert w.dtype == y.dtype
+        w = w.contiguous()
+    T = int(task_begin.shape[0])
+    assert task_begin.dtype == task_end.dtype == perm.dtype == torch.int64 and task_end.shape[0] == T
+    K = r0 * r1
+    Gp = torch.empty((T, K, K), dtype=L.dtype, device=L.device)
+    hp = torch.empty((T, K), dtype=L.dtype, device=L.device)
+    _check(lib().ttr_als_normal(dt, T, r0, r1, L.data_ptr(), ldl, R.data_ptr(), ldr, w.data_ptr() if w is not None else None,
+                                y.data_ptr(), perm.contiguous().data_ptr(), task_begin.contiguous().data_ptr(),
+                                task_end.contiguous().data_ptr(), Gp.data_ptr(), hp.data_ptr(), _stream()), "ttr_als_normal")
+    return Gp, hp
+
+
+def _xout(X: torch.Tensor, inner: int):
+    """(item, k) -> X[item, k // inner, k % inner] for a [n_items, K // inner, inner] view X (any strides)."""
+    assert X.dim() == 3 and X.shape[2] == inner
+    return int(inner), int(X.stride(0)), int(X.stride(1)), int(X.stride(2))
+
+
+@_on_device
+def spd_solve(Gp: torch.Tensor, hp: torch.Tensor, part_off: torch.Tensor, part_base: int, X: torch.Tensor, inner: int,
+              Gsum: torch.Tensor, hsum: torch.Tensor, status: torch.Tensor, counts: Optional[torch.Tensor] = None) -> None:
+    """ttr_spd_solve: item i solves (sum of Gp[part_off[i] - part_base : part_off[i+1] - part_base]) x = (sum of hp ...) by Cholesky
+    into X[i] (a [n_items, K // inner, inner] view, any strides); status[i] = 1 solved, 0 flagged (then Gsum[i] / hsum[i] hold the
+    summed system and X[i] is not written).  ``counts`` (int64 [n], optional): samples per item; fewer than K flag the item."""
+    dt = dtype_code(Gp.dtype)
+    n, K = int(Gsum.shape[0]), int(Gp.shape[-1])
+    assert Gp.is_contiguous() and hp.is_contiguous() and Gsum.is_contiguous() and hsum.is_contiguous()
+    assert part_off.dtype == torch.int64 and part_off.is_contiguous() and part_off.shape[0] == n + 1
+    assert status.dtype == torch.int32 and status.is_contiguous() and status.shape[0] == n and X.shape[0] == n
+    if counts is not None:
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape[0] == n
+    _check(lib().ttr_spd_solve(dt, n, K, Gp.data_ptr(), hp.data_ptr(), part_off.data_ptr(), int(part_base), X.data_ptr(),
+                               *_xout(X, inner), Gsum.data_ptr(), hsum.data_ptr(), status.data_ptr(),
+                               counts.data_ptr() if counts is not None else None, _stream()), "ttr_spd_solve")
+
+
+@_on_device
+def pinv_finish(V: torch.Tensor, sigma: torch.Tensor, t: torch.Tensor, status: torch.Tensor, X: torch.Tensor, inner: int) -> None:
+    """ttr_pinv_finish: X[i] = V[i] diag(lambda+) t[i] for the items with status 0 (lambda = sigma^2, cut at K eps lambda_max)."""
+    dt = dtype_code(V.dtype)
+    n, K = int(V.shape[0]), int(V.shape[-1])
+    assert V.is_contiguous() and sigma.is_contiguous() and t.is_contiguous() and t.numel() == n * K
+    _check(lib().ttr_pinv_finish(dt, n, K, V.data_ptr(), sigma.data_ptr(), t.data_ptr(), status.data_ptr(), X.data_ptr(),
+                                 *_xout(X, inner), _stream()), "ttr_pinv_finish")
 
 
 KNOB_QR_PANEL = 0

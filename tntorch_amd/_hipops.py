@@ -28,6 +28,8 @@ Algorithms (reference call sites in brackets):
 * ``cp_als``        CP-ALS with a fused MTTKRP                                [tensor.py:210-400]
 * ``decompress`` / ``dot`` / ``core_kron``  consumers and producers     [tensor.py:1639-1687, metrics.py:28-116,
                     tensor.py:2309-2320]
+* ``als_core``      the per-slice least-squares core update of TT completion: normal equations on the matrix cores,
+                    batched Cholesky, minimum-norm fallback for rank-deficient slices  [interpolation.py:71-90]
 """
 
 from __future__ import annotations
@@ -1836,3 +1838,93 @@ def maxvol(A3: torch.Tensor, tol: float, max_iters: int):
 def gather_step(X: torch.Tensor, xrow, G: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """Y[p] = X[xrow[p]] @ G[:, idx[p], :] (ttr_gather_step; xrow None: X[p])."""
     return _hip.gather_step(X, xrow, G, idx)
+
+
+# ------------------------------------------------------------------------------------------------ TT completion (ALS)
+ALS_WORKSPACE_BYTES = 1 << 30  # device bytes of one core step's systems; a step above it runs in chunks of slices
+ALS_TASK_SAMPLES = 1024  # samples per ttr_als_normal task (at least; 16 K for K > 64): long slices are split into several
+
+
+class AlsPlan:
+    """Tasks and slice chunks of one mode for a given K: built on the host from the per-slice sample counts (read back once per
+    call), uploaded once.  ``chunks``: (i0, i1, t0, t1) = slices [i0, i1) and their tasks [t0, t1)."""
+
+    def __init__(self, counts: Sequence[int], K: int, elem: int, device):
+        ts = max(ALS_TASK_SAMPLES, 16 * K)
+        tb, te, toff, pos = [], [], [0], 0
+        for n in counts:
+            nt = max(1, -(-int(n) // ts))
+            for k in range(nt):
+                tb.append(pos + (n * k) // nt)
+                te.append(pos + (n * (k + 1)) // nt)
+            pos += int(n)
+            toff.append(len(tb))
+        self.chunks = []
+        i0, I = 0, len(counts)
+        per = K * K * elem
+        while i0 < I:
+            i1 = i0 + 1
+            while i1 < I and ((toff[i1 + 1] - toff[i0]) + 3 * (i1 + 1 - i0)) * per <= ALS_WORKSPACE_BYTES:
+                i1 += 1
+            self.chunks.append((i0, i1, toff[i0], toff[i1]))
+            i0 = i1
+        self.tb = torch.tensor(tb, dtype=torch.int64, device=device)
+        self.te = torch.tensor(te, dtype=torch.int64, device=device)
+        self.toff = torch.tensor(toff, dtype=torch.int64, device=device)
+        self.counts = torch.tensor([int(n) for n in counts], dtype=torch.int64, device=device)
+
+
+def als_normal(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: torch.Tensor, perm: torch.Tensor, plan: AlsPlan):
+    """Summed per-slice systems G [I, K, K], h [I, K] of one mode (ttr_als_normal per chunk; the partials of a slice's tasks are
+    added with ``index_add_``).  Test and benchmark helper: the ALS step itself sums them inside ttr_spd_solve."""
+    K = L.shape[1] * R.shape[1]
+    I = plan.toff.shape[0] - 1
+    G = torch.zeros((I, K, K), dtype=L.dtype, device=L.device)
+    h = torch.zeros((I, K), dtype=L.dtype, device=L.device)
+    owner = torch.repeat_interleave(torch.arange(I, device=L.device), plan.toff[1:] - plan.toff[:-1])
+    for i0, i1, t0, t1 in plan.chunks:
+        Gp, hp = _hip.als_normal(L, R, w, y, perm, plan.tb[t0:t1], plan.te[t0:t1])
+        G.index_add_(0, owner[t0:t1], Gp)
+        h.index_add_(0, owner[t0:t1], hp)
+    return G, h
+
+
+def spd_solve_batch(Gp: torch.Tensor, hp: torch.Tensor, part_off: torch.Tensor, X: torch.Tensor, inner: int,
+                    counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_spd_solve on systems given as partials, with the minimum-norm fallback of the flagged items; X [n, K // inner, inner]
+    is written in place.  Returns status (int32 [n]: 1 Cholesky, 0 fallback).  No host synchronisation."""
+    n, K = X.shape[0], Gp.shape[-1]
+    Gsum = torch.empty((n, K, K), dtype=Gp.dtype, device=Gp.device)
+    hsum = torch.empty((n, K), dtype=Gp.dtype, device=Gp.device)
+    status = torch.empty(n, dtype=torch.int32, device=Gp.device)
+    _hip.spd_solve(Gp, hp, part_off, int(0), X, inner, Gsum, hsum, status, counts)
+    _pinv_fallback(Gsum, hsum, status, X, inner)
+    return status
+
+
+def _pinv_fallback(Gsum, hsum, status, X, inner):
+    """Items with status 0: X = G+ h through ttr_eigh_trunc (accepted items skipped), ttr_gemm and ttr_pinv_finish."""
+    n, K = Gsum.shape[0], Gsum.shape[-1]
+    V, sig, _ = _hip.eigh_trunc(Gsum, _hip.EIG_RAW, False, 0.0, K, abs_floor=_hip.SOLVER_JACOBI_ABS, skip_items=status,
+                                sigma_in=torch.zeros((n, K), dtype=Gsum.dtype, device=Gsum.device))
+    t = _hip.gemm(V, hsum[:, :, None], transA=True)
+    _hip.pinv_finish(V, sig, t, status, X, inner)
+
+
+def als_core(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: torch.Tensor, perm: torch.Tensor, plan: AlsPlan,
+             I: int) -> torch.Tensor:
+    """The least-squares core [r0, I, r1] of one ALS step (interpolation.py:71-90 with the (a, b) ordering fixed): a fresh tensor,
+    slice i solved from the samples of plan's tasks.  No host synchronisation."""
+    r0, r1 = L.shape[1], R.shape[1]
+    K = r0 * r1
+    core = torch.empty((r0, I, r1), dtype=L.dtype, device=L.device)
+    for i0, i1, t0, t1 in plan.chunks:
+        n = i1 - i0
+        Gp, hp = _hip.als_normal(L, R, w, y, perm, plan.tb[t0:t1], plan.te[t0:t1])
+        X = core[:, i0:i1, :].permute(1, 0, 2)
+        Gsum = torch.empty((n, K, K), dtype=L.dtype, device=L.device)
+        hsum = torch.empty((n, K), dtype=L.dtype, device=L.device)
+        status = torch.empty(n, dtype=torch.int32, device=L.device)
+        _hip.spd_solve(Gp, hp, plan.toff[i0 : i1 + 1], t0, X, r1, Gsum, hsum, status, plan.counts[i0:i1])
+        _pinv_fallback(Gsum, hsum, status, X, r1)
+    return core

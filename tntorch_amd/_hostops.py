@@ -450,3 +450,29 @@ def maxvol(A3: torch.Tensor, tol: float, max_iters: int):
     """maxvol.py:115-170 on every item of [B, N, r] (N > r) -> index [B, r] int64, C [B, N, r]."""
     out = [_maxvol_one(a, tol, max_iters) for a in A3]
     return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
+
+
+def als_core(L: torch.Tensor, R: torch.Tensor, w: torch.Tensor, y: torch.Tensor, order: torch.Tensor, off: Sequence[int],
+             I: int) -> torch.Tensor:
+    """interpolation.py:71-90 with the design columns in (a, b) order: slice i of the new core [r0, I, r1] is the minimum-norm
+    least-squares solution (gelsd) over the samples order[off[i]:off[i+1]], row k_p = w_p (L_p (x) R_p), k_p[a r1 + b] =
+    w_p L_p[a] R_p[b], right-hand side w_p y_p.  A fresh tensor."""
+    r0, r1 = L.shape[1], R.shape[1]
+    core = torch.empty((r0, I, r1), dtype=L.dtype)
+    for i in range(I):
+        idx = order[off[i] : off[i + 1]]
+        A = torch.reshape(L[idx, :, None] * R[idx, None, :], [len(idx), -1]) * w[idx, None]
+        b = y[idx] * w[idx]
+        sol = torch.linalg.lstsq(A, b[:, None], driver="gelsd").solution[:, 0]
+        core[:, i, :] = torch.reshape(sol, (r0, r1))
+    return core
+
+
+def als_left_step(L: torch.Tensor, core: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """lefts[mu + 1] = lefts[mu] @ core[:, X[:, mu], :] (interpolation.py:84-87) on [P, r] interfaces."""
+    return torch.einsum("pa,apb->pb", L, core[:, x, :])
+
+
+def als_right_step(R: torch.Tensor, core: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """rights[mu - 1] = core[:, X[:, mu], :] @ rights[mu] (interpolation.py:67-70, 88-91) on [P, r] interfaces."""
+    return torch.einsum("apb,pb->pa", core[:, x, :], R)
