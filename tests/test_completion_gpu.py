@@ -5,7 +5,8 @@ import torch
 
 import tntorch_amd as tn
 from tntorch_amd import _hipops
-from test_completion_host import (_f64_default, case_args, fixture, oracle_case, recovery_data, rel, values)  # noqa: F401
+from test_completion_host import (_f64_default, case_args, fixture, oracle_case, recovery_data, rel, solve_lds_max_k,  # noqa: F401
+                                  values)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -42,7 +43,8 @@ def check_normal(r0, r1, dtype, weighted, P=3000, I=5, x=None, seed=0):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
-@pytest.mark.parametrize("r0,r1", [(1, 1), (1, 7), (5, 1), (3, 5), (8, 8), (7, 13), (16, 16), (32, 32)])
+@pytest.mark.parametrize("r0,r1", [(1, 1), (1, 7), (5, 1), (3, 5), (8, 8), (7, 13), (16, 16), (32, 32), (1, 1024), (1024, 1),
+                                   (64, 16), (16, 64), (31, 33), (2, 512), (1, 16), (1, 17), (17, 1), (4, 4)])
 @pytest.mark.parametrize("weighted", [False, True])
 def test_als_normal_matches_explicit_design(r0, r1, dtype, weighted):
     check_normal(r0, r1, dtype, weighted, P=2000 if r0 * r1 > 256 else 3000, I=3 if r0 * r1 > 256 else 5)
@@ -88,25 +90,34 @@ def spd_case(K, n_items, seed, deficient):
     return As, bs, torch.stack(Gs), torch.stack(hs), torch.tensor(counts)
 
 
-@pytest.mark.parametrize("K", [6, 64, 100])
-def test_spd_solve_and_minimum_norm_fallback(K):
+@pytest.mark.parametrize("dtype,K", [(dt, K) for dt in (torch.float64, torch.float32)
+                                     for K in (6, 64, 100, solve_lds_max_k(dt), solve_lds_max_k(dt) + 1)])
+def test_spd_solve_and_minimum_norm_fallback(dtype, K):
+    """fp32 partials (rounded from the fp64 ones): Cholesky within K eps cond(G), the minimum-norm items within K eps cond_r (the
+    retained spectrum) of the fp64 references (C = 1; the measured constants are in test_completion_kernels_gpu)."""
     n = 7
     deficient = {1, 4}
     As, bs, Gp, hp, counts = spd_case(K, n, K, deficient)
-    X = torch.full((n, 1, K), float("nan"), dtype=torch.float64, device=DEV)
+    Gp, hp = Gp.to(dtype), hp.to(dtype)
+    X = torch.full((n, 1, K), float("nan"), dtype=dtype, device=DEV)
     status = _hipops.spd_solve_batch(Gp.to(DEV), hp.to(DEV), torch.arange(0, 2 * n + 1, 2, device=DEV), X, K,
                                      counts=counts.to(DEV))
-    st, X = status.cpu().tolist(), X.cpu()[:, 0, :]
+    st, X = status.cpu().tolist(), X.cpu()[:, 0, :].double()
+    eps32 = 2.0 ** -23
     for i in range(n):
-        G, h = Gp[2 * i] + Gp[2 * i + 1], hp[2 * i] + hp[2 * i + 1]
+        G, h = Gp[2 * i].double() + Gp[2 * i + 1].double(), hp[2 * i].double() + hp[2 * i + 1].double()
         if i in deficient:
             assert st[i] == 0
             ref = torch.linalg.lstsq(As[i], bs[i][:, None], driver="gelsd").solution[:, 0]
-            assert float((X[i] - ref).norm()) <= 1e-8 * float(ref.norm())
+            sv = torch.linalg.svdvals(As[i])
+            tol = 1e-8 if dtype == torch.float64 else K * eps32 * float(sv[0] / sv[-1]) ** 2
+            assert float((X[i] - ref).norm()) <= tol * float(ref.norm())
         else:
             assert st[i] == 1
             ref = torch.linalg.solve(G, h)
-            assert float((X[i] - ref).norm()) <= 1e-9 * float(ref.norm())
+            lam = torch.linalg.eigvalsh(G)
+            tol = 1e-9 if dtype == torch.float64 else K * eps32 * float(lam[-1] / lam[0])
+            assert float((X[i] - ref).norm()) <= tol * float(ref.norm())
 
 
 def test_spd_solve_flags_degenerate_design_by_pivot():

@@ -1,5 +1,7 @@
 """TT completion (tn.als_completion) on the CPU: replay of the reference's fixture, an explicit Khatri-Rao ALS oracle, recovery of
-an exact low-rank tensor, minimum-norm slices, the printed eps, and the error / x0 contract."""
+an exact low-rank tensor, minimum-norm slices, the printed eps, and the error / x0 contract.  Also the device plan (AlsPlan: tasks
+and chunks) on a CPU device and the argument envelope of the three completion entries of the C ABI."""
+import ctypes
 import os
 import re
 
@@ -8,9 +10,31 @@ import pytest
 import torch
 
 import tntorch_amd as tn
-from tntorch_amd import _hostops
+from tntorch_amd import _hip, _hipops, _hostops
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "completion_f64.npz")
+
+# The documented shape rules of csrc/ttr_complete.hip, restated so that tests can bracket them
+MAX_K = 1024  # r0 * r1 limit of all three entries
+STAGE_BYTES = 48 * 1024  # LDS of ttr_als_normal's staged sample rows
+SOLVE_LDS_BYTES = 60 * 1024  # ttr_spd_solve keeps (K * K + K) elements in LDS up to this size, global memory above
+
+
+def elem_size(dtype):
+    return torch.empty((), dtype=dtype).element_size()
+
+
+def stage_rows(r0, r1, dtype):
+    """Samples ttr_als_normal stages per pass: min(256, 48 KiB / ((r0 + r1 + 1) elem + 8)), rounded down to a multiple of 4."""
+    return min(256, STAGE_BYTES // ((r0 + r1 + 1) * elem_size(dtype) + 8)) & ~3
+
+
+def solve_lds_max_k(dtype):
+    """The largest K whose system ttr_spd_solve factors in LDS; K + 1 runs in global memory."""
+    K = 1
+    while ((K + 1) * (K + 1) + (K + 1)) * elem_size(dtype) <= SOLVE_LDS_BYTES:
+        K += 1
+    return K
 
 
 @pytest.fixture(autouse=True)
@@ -203,3 +227,89 @@ def test_errors_and_x0_contract():
     Xi = torch.tensor([[0, 0], [1, 1], [2, 2]], dtype=torch.int32)
     t = tn.als_completion(Xi, torch.ones(3, dtype=torch.float64), ranks_tt=1, verbose=False)
     assert list(t.shape) == [3, 3]
+
+
+# ------------------------------------------------------------------------------------------------------------ device plan
+@pytest.mark.parametrize("K", [1, 6, 96])
+@pytest.mark.parametrize("budget", [1, 40 * 96 * 96 * 8, 1 << 40])
+def test_als_plan_tasks_and_chunks(K, budget, monkeypatch):
+    """Tasks partition every slice's samples in order (an empty slice: one empty task), none longer than max(ALS_TASK_SAMPLES,
+    16 K); the chunks partition the slices, each within the byte budget of its systems or a single slice."""
+    monkeypatch.setattr(_hipops, "ALS_TASK_SAMPLES", 40)
+    monkeypatch.setattr(_hipops, "ALS_WORKSPACE_BYTES", budget)
+    ts = max(40, 16 * K)
+    counts = [0, 1, ts, ts + 1, 0, 3 * ts + 5, 7, ts - 1, 2 * ts, 0]
+    elem = 8
+    plan = _hipops.AlsPlan(counts, K, elem, torch.device("cpu"))
+    tb, te, toff = plan.tb.tolist(), plan.te.tolist(), plan.toff.tolist()
+    assert plan.counts.tolist() == counts
+    assert len(toff) == len(counts) + 1 and toff[0] == 0 and len(tb) == len(te) == toff[-1]
+    pos = 0
+    for i, n in enumerate(counts):
+        t0, t1 = toff[i], toff[i + 1]
+        assert t1 - t0 == max(1, -(-n // ts)), (i, n)
+        assert tb[t0] == pos and te[t1 - 1] == pos + n, (i, n)
+        for t in range(t0, t1):
+            assert 0 <= te[t] - tb[t] <= ts and (n == 0 or te[t] > tb[t]), (i, t)
+            assert t == t0 or tb[t] == te[t - 1], (i, t)
+        pos += n
+    nxt = 0
+    for i0, i1, t0, t1 in plan.chunks:
+        assert i0 == nxt and i1 > i0 and (t0, t1) == (toff[i0], toff[i1])
+        assert ((t1 - t0) + 3 * (i1 - i0)) * K * K * elem <= budget or i1 - i0 == 1, (i0, i1)
+        nxt = i1
+    assert nxt == len(counts)
+    if budget == 1:
+        assert len(plan.chunks) == len(counts)
+    if budget == 1 << 40:
+        assert len(plan.chunks) == 1
+
+
+# ------------------------------------------------------------------------------------------------------------ C-ABI envelope
+@pytest.fixture(scope="module")
+def cabi():
+    """The cross-compiled library, loaded without a device: every call below returns from its argument checks."""
+    import __graft_entry__ as g
+
+    g.build()
+    L = ctypes.CDLL(g.LIB)
+    for name in ("ttr_als_normal", "ttr_spd_solve", "ttr_pinv_finish"):
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = _hip._SIGNATURES[name]
+    L.ttr_last_error.restype = ctypes.c_char_p
+    return L
+
+
+def abi_code(name):
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ttround_hip.h")).read()
+    return int(re.search(r"#define\s+" + name + r"\s+\(?(-?\d+)\)?", src).group(1))
+
+
+def test_completion_entries_argument_envelope(cabi):
+    OK, INVALID, UNSUPPORTED = abi_code("TTR_OK"), abi_code("TTR_E_INVALID"), abi_code("TTR_E_UNSUPPORTED")
+    nul = [None] * 8
+
+    def normal(dt, ntasks, r0, r1, ldl, ldr):
+        return cabi.ttr_als_normal(dt, ntasks, r0, r1, None, ldl, None, ldr, *nul)
+
+    def solve(dt, n, K):
+        return cabi.ttr_spd_solve(dt, n, K, None, None, None, 0, None, 1, K, 1, 1, None, None, None, None, None)
+
+    def finish(dt, n, K):
+        return cabi.ttr_pinv_finish(dt, n, K, None, None, None, None, None, 1, K, 1, 1, None)
+
+    for dt in (_hip.F32, _hip.F64):
+        for r0, r1 in ((1, MAX_K + 1), (MAX_K + 1, 1), (32, 33)):
+            assert normal(dt, 1, r0, r1, r0, r1) == UNSUPPORTED, (dt, r0, r1)
+        assert b"above" in cabi.ttr_last_error()
+        assert solve(dt, 1, MAX_K + 1) == UNSUPPORTED and solve(dt, 0, MAX_K + 1) == UNSUPPORTED
+        assert finish(dt, 1, MAX_K + 1) == UNSUPPORTED and finish(dt, 0, MAX_K + 1) == UNSUPPORTED
+        # K = 1024 passes the size checks and stops at the NULL pointers (no HIP call either way)
+        assert normal(dt, 1, 1, MAX_K, 1, MAX_K) == INVALID and b"NULL" in cabi.ttr_last_error()
+        assert solve(dt, 1, MAX_K) == INVALID and b"NULL" in cabi.ttr_last_error()
+        assert finish(dt, 1, MAX_K) == INVALID and b"NULL" in cabi.ttr_last_error()
+        assert normal(dt, 1, 4, 3, 3, 3) == INVALID and normal(dt, 1, 4, 3, 4, 2) == INVALID and normal(dt, -1, 4, 3, 4, 3) == INVALID
+        assert normal(dt, 0, 4, 3, 4, 3) == OK and normal(dt, 0, 1, MAX_K, 1, MAX_K) == OK
+        assert solve(dt, 0, 16) == OK and solve(dt, 0, MAX_K) == OK
+        assert finish(dt, 0, 16) == OK and finish(dt, 0, MAX_K) == OK
+    assert normal(2, 0, 4, 3, 4, 3) == INVALID and solve(2, 0, 16) == INVALID and finish(2, 0, 16) == INVALID
