@@ -37,6 +37,97 @@ def test_binding_matches_header(lib):
     assert sorted(_hip.EXPORTED_SYMBOLS) == declared_functions()
 
 
+def _header_defines():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return {n: int(v) for n, v in re.findall(r"^#define\s+(TTR_\w+)\s+\(?(-?\d+)\)?\s*$", src, flags=re.M)}
+
+
+def test_parser_finds_every_declaration_once():
+    """The binding's table is what its parser reads from the header: the names of ``declared_functions()``, one signature each."""
+    from tntorch_amd import _hip
+
+    sigs, defines = _hip._parse_header(open(HEADER).read())
+    assert sorted(sigs) == declared_functions()
+    assert sigs == _hip._SIGNATURES and _hip.EXPORTED_SYMBOLS == tuple(sigs)
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert len(re.findall(r"\bttr_[a-z0-9_]+\s*\(", src)) == len(sigs)   # no name is declared twice
+    assert defines == _header_defines()
+
+
+def test_parsed_signatures_pinned():
+    """Written out by hand from the header, one entry per shape the parser has to handle: (void), a const char* result, an
+    int64_t result, doubles, pointers to pointers, typed out-pointers, and the longest recent declaration."""
+    from ctypes import c_char_p, c_double, c_int, c_int64, c_void_p
+
+    from tntorch_amd import _hip
+
+    i, q, d, p = c_int, c_int64, c_double, c_void_p
+    pins = {
+        "ttr_version": (i, []),
+        "ttr_last_error": (c_char_p, []),
+        "ttr_gemm_workspace_bytes": (q, [i, q, q, q, q]),
+        "ttr_gemm_axpby": (i, [i, i, i, q, q, q, p, q, q, p, q, q, p, q, q, d, d, q, p, q, p]),
+        "ttr_round_tt_workspace_bytes": (q, [i, q, p, p, q, i]),
+        "ttr_round_tt": (i, [i, q, p, q, p, p, i, i, d, d, i, p, p, p, p, q, p]),
+        "ttr_prof_collect": (i, [p, p]),
+        "ttr_als_normal": (i, [i, q, q, q, p, q, p, q, p, p, p, p, p, p, p, p]),
+    }
+    for name, sig in pins.items():
+        assert _hip._SIGNATURES[name] == sig, name
+
+
+def test_constants_come_from_the_header():
+    from tntorch_amd import _hip
+
+    defines = _header_defines()
+    assert len(defines) >= 48
+    for name, value in defines.items():
+        assert getattr(_hip, name[len("TTR_"):]) == value, name
+    assert _hip.PROF_KINDS == ("gemm", "qr_factor", "qr_apply", "eigh", "misc", "rotgram", "project", "rowgram")
+    assert len(_hip.PROF_KINDS) == defines["TTR_PROF_NKINDS"]
+
+
+@pytest.mark.parametrize("text, quoted", [
+    ("int ttr_foo(int dtype, float x);", "float x"),                       # a type outside the map
+    ("int ttr_foo(struct ttr_shape s);", "struct ttr_shape s"),
+    ("int ttr_foo(int dtype, const struct ttr_shape* s);", "const struct ttr_shape* s"),
+    ("unsigned ttr_foo(void);", "unsigned"),
+    ("int ttr_foo(int (*callback)(int), void* stream);", "int (*callback)(int)"),   # a ttr_foo( that is not a plain declaration
+    ("int ttr_foo(int dtype, void* stream)\nint ttr_bar(void);", "ttr_foo(int dtype, void* stream)"),
+    ("int ttr_foo();", "''"),
+    ("#define TTR_FOO 1.5\n", "TTR_FOO 1.5"),
+])
+def test_parser_rejects_what_it_does_not_know(text, quoted):
+    from tntorch_amd import _hip
+
+    with pytest.raises(ValueError) as e:
+        _hip._parse_header("#include <stdint.h>\nint ttr_ok(const void* const* p, int64_t* q, double v[3]);\n" + text)
+    assert quoted in str(e.value)
+
+
+def test_no_bare_knob_ids_or_status_codes_in_the_binding():
+    """Knob ids and status codes are spelled by their header names in _hip.py, never as numbers."""
+    src = open(os.path.join(ROOT, "tntorch_amd", "_hip.py")).read()
+    src = re.sub(r"#[^\n]*", "", src)   # (comments quote the TTR_KNOBS syntax with numbers)
+    knob_calls = re.findall(r"ttr_debug_set_knob\(\s*([^,)]*)", src)
+    comparisons = re.findall(r"\bcode\s*[=!<>]=?\s*([^\s:)]+)", src)
+    assert len(knob_calls) >= 4 and len(comparisons) >= 3
+    for operand in knob_calls:
+        assert not re.fullmatch(r"\(?-?\d+\)?", operand.strip()), f"ttr_debug_set_knob({operand}, ...)"
+    for operand in comparisons:
+        assert operand == "0" or not re.fullmatch(r"\(?-?\d+\)?", operand), f"code compared with {operand}"
+
+
+def test_call_helper_only_launches_streamed_entries():
+    """``_hip._call`` appends the current stream: every entry it is used for ends in ``void* stream`` in the header."""
+    src = open(os.path.join(ROOT, "tntorch_amd", "_hip.py")).read()
+    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names = set(re.findall(r'_call\("(ttr_\w+)"', src))
+    assert len(names) >= 30
+    for n in names:
+        assert re.search(rf"\b{n}\s*\([^()]*\bvoid\*\s*stream\s*\)\s*;", header), n
+
+
 def test_host_only_entry_points(lib):
     lib.ttr_version.restype = ctypes.c_int
     from tntorch_amd import _hip

@@ -3,12 +3,16 @@
 There is no fallback: a CUDA/HIP tensor reaching the hot path without the built
 library raises ``RuntimeError``.  Torch is used here only for device memory
 (``torch.empty``) and to obtain the current HIP stream.
+
+The header is the only statement of the ABI: every signature (``_SIGNATURES``) and every constant (``TTR_X`` is ``X`` here)
+is parsed from it at import, so a new entry point is declared in the header and gets its wrapper below, nothing else.
 """
 
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 from ctypes import c_char_p, c_double, c_int, c_int64, c_void_p
 from typing import Optional, Tuple
 
@@ -18,211 +22,58 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TTR_LIB_PATH: load another build of the same library (kernel experiments: several variants side by side)
 LIB_PATH = os.environ.get("TTR_LIB_PATH") or os.path.join(_HERE, "libttround_hip.so")
 
-F32, F64 = 0, 1
-ABI_VERSION = 14  # include/ttround_hip.h: TTR_ABI_VERSION
-SCALE_NONE, SCALE_MUL, SCALE_DIV = 0, 1, 2
-EIG_RAW, EIG_REF, EIG_MATCH_DIAG = 0, 1, 2
-SOLVER_JACOBI_REL, SOLVER_JACOBI_ABS, SOLVER_TRIDIAG, SOLVER_JACOBI_LIVE = 0, 1, 2, 3  # `abs_floor` argument of ttr_eigh_trunc
-PROF_KINDS = ("gemm", "qr_factor", "qr_apply", "eigh", "misc", "rotgram", "project", "rowgram")
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ttround_hip.h")
+_SCALARS = {"int": c_int, "int64_t": c_int64, "double": c_double}
+_POINTEES = ("void", "char", "int", "int32_t", "int64_t", "double")
+_C_DECL = re.compile(r"(const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)(?:\w+\s*)?((?:\[\w*\]\s*)*)")
+
+
+def _ctype(text: str):
+    """ctypes type of a C return type or of one parameter (its name is dropped): the scalars of ``_SCALARS``, ``const char*``
+    -> c_char_p, every other pointer or array of a ``_POINTEES`` type -> c_void_p; anything else is an error."""
+    m = _C_DECL.fullmatch(text.strip())
+    if m:
+        const, base, stars, dims = m.groups()
+        if (stars or dims) and base in _POINTEES:
+            return c_char_p if const and base == "char" and stars.strip() == "*" and not dims else c_void_p
+        if not (stars or dims or const) and base in _SCALARS:
+            return _SCALARS[base]
+    raise ValueError(f"include/ttround_hip.h: no ctypes mapping for {text.strip()!r}")
+
+
+def _parse_header(text: str):
+    """({name: (restype, [argtypes])} of every ``ttr_*`` declaration, {name: value} of every ``#define TTR_X <integer>``) of
+    the header's text.  Whatever is neither (after comments, other preprocessor lines and the extern "C" braces) is an error."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(TTR_\w+)(.*)$", text, flags=re.M):
+        m = re.fullmatch(r"\s+(?:(-?\d+)|\((-?\d+)\))\s*", value)
+        if not m or name in defines:
+            raise ValueError(f"include/ttround_hip.h: #define {name}{value}: not one integer constant")
+        defines[name] = int(m.group(1) or m.group(2))
+    code = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    code = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", code, flags=re.S)
+    signatures = {}
+    for stmt in filter(None, (st.strip() for st in code.split(";"))):
+        m = re.fullmatch(r"([^()]+?)\b(ttr_\w+)\s*\(([^()]*)\)", stmt)
+        if not m or m.group(2) in signatures:
+            raise ValueError(f"include/ttround_hip.h: not a (single) declaration of a ttr_* function: {stmt!r}")
+        res, name, params = m.groups()
+        signatures[name] = (_ctype(res), [] if params.strip() == "void" else [_ctype(a) for a in params.split(",")])
+    return signatures, defines
+
 
 _lib = None
 
-# name -> (restype, argtypes); mirrors include/ttround_hip.h one to one
-_SIGNATURES = {
-    "ttr_version": (c_int, []),
-    "ttr_last_error": (c_char_p, []),
-    "ttr_qr_max_cols": (c_int, [c_int]),
-    "ttr_eigh_max_n_lds": (c_int, [c_int]),
-    "ttr_eigh_max_n": (c_int, [c_int]),
-    "ttr_gemm_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64, c_int64]),
-    "ttr_gemm": (
-        c_int,
-        [c_int, c_int, c_int, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
-         c_int64, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_gemm_axpby": (
-        c_int,
-        [c_int, c_int, c_int, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_double, c_double, c_int64, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_qr_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64]),
-    "ttr_qr": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_qr_t": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_qr_factor": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_qr_factor_expo": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_void_p, c_void_p],
-    ),
-    "ttr_qr_apply": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64,
-         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p],
-    ),
-    "ttr_qr_pushed_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64]),
-    "ttr_qr_factor_pushed": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_qr_factor_pushed_expo": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_void_p, c_void_p],
-    ),
-    "ttr_qr_factor_pushed_sum": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_qr_apply_pushed": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64,
-         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p],
-    ),
-    "ttr_qr_apply_pushed_gram_parts": (c_int64, [c_int, c_int64, c_int64, c_int64, c_int64]),
-    "ttr_qr_apply_pushed_gram": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64,
-         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p],
-    ),
-    "ttr_eigh_workspace_bytes": (c_int64, [c_int, c_int64, c_int64]),
-    "ttr_eigh_trunc": (
-        c_int,
-        [c_int, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-         c_int, c_int, c_double, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_carry_rows32": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
-    "ttr_spectrum_flat": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_double, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ttr_eigh_top_ok": (c_int, [c_int64, c_int64]),
-    "ttr_eigh_top": (
-        c_int,
-        [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
-         c_void_p, c_int64, c_double, c_void_p, c_int, c_void_p],
-    ),
-    "ttr_eigsel_max_n": (c_int, []),
-    "ttr_eigsel_scratch_bytes": (c_int64, [c_int, c_int64, c_int64]),
-    "ttr_tridiag_workspace_bytes": (c_int64, [c_int, c_int64, c_int64]),
-    "ttr_tridiag": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "ttr_tri_eigsel": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "ttr_tridiag_back": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "ttr_bj_scratch_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64]),
-    "ttr_bj_solve": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ttr_bj_apply": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "ttr_bj_control": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p]),
-    "ttr_sweep_gram_parts": (c_int64, [c_int64, c_int64]),
-    "ttr_rowgram": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
-    "ttr_qr_pushed_flag_offset": (c_int64, [c_int, c_int64, c_int64, c_int64]),
-    "ttr_rotgram": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
-    ),
-    "ttr_project": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p],
-    ),
-    "ttr_colgram_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64]),
-    "ttr_colgram": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
-    ),
-    "ttr_colproject": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p],
-    ),
-    "ttr_pow2_normalize": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "ttr_scale_batch": (
-        c_int,
-        [c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_orth_fixup_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64, c_int64]),
-    "ttr_orth_fixup": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_double, c_void_p,
-         c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_norm": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
-    "ttr_scale_cols": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int,
-         c_void_p, c_int64, c_int64, c_void_p],
-    ),
-    "ttr_mask_cols": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
-    "ttr_krp_contract": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "ttr_hadamard": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ttr_core_kron": (c_int, [c_int] + [c_int64] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ttr_round_tt_workspace_bytes": (c_int64, [c_int, c_int64, c_void_p, c_void_p, c_int64, c_int]),
-    "ttr_round_tt": (
-        c_int,
-        [c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_void_p,
-         c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_gather_chain_workspace_bytes": (c_int64, [c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64]),
-    "ttr_gather_chain": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p],
-    ),
-    "ttr_gather_step": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
-         c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
-    ),
-    "ttr_maxvol_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64]),
-    "ttr_maxvol": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-         c_int64, c_void_p],
-    ),
-    "ttr_als_normal_groups": (c_int64, [c_int64, c_int64]),
-    "ttr_als_normal": (
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-         c_void_p, c_void_p, c_void_p],
-    ),
-    "ttr_spd_solve": (
-        c_int,
-        [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "ttr_pinv_finish": (
-        c_int,
-        [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p],
-    ),
-    "ttr_debug_set_qr_stamps": (c_int, [c_void_p]),
-    "ttr_debug_set_knob": (c_int, [c_int, c_int]),
-    "ttr_prof_enable": (c_int, [c_int]),
-    "ttr_prof_collect": (c_int, [ctypes.POINTER(c_double), ctypes.POINTER(c_int64)]),
-    "ttr_prof_collect_work": (c_int, [ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
-}
+# name -> (restype, argtypes) of every entry point and TTR_X -> value of every constant: read from the header, which is the
+# only statement of the ABI.  Every TTR_X is X here (F32, SCALE_MUL, EIG_RAW, SOLVER_TRIDIAG, ALG_SVD, KNOB_QR_PACK, E_INVALID, ...)
+with open(_HEADER) as _f:
+    _SIGNATURES, _DEFINES = _parse_header(_f.read())
+globals().update({k[len("TTR_"):]: v for k, v in _DEFINES.items()})
+PROF_KINDS = tuple(k[len("TTR_PROF_"):].lower() for k in sorted(_DEFINES, key=_DEFINES.get)
+                   if k.startswith("TTR_PROF_") and k != "TTR_PROF_NKINDS")
+if len(PROF_KINDS) != _DEFINES["TTR_PROF_NKINDS"]:
+    raise ValueError(f"include/ttround_hip.h: TTR_PROF_NKINDS = {_DEFINES['TTR_PROF_NKINDS']}, but the kinds are {PROF_KINDS}")
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -259,10 +110,10 @@ def lib():
         # default since round 6: the reference's ranks).  TTR_STRICT_RANKS=0 switches the floor off: exact zeros are cut
         # (INTEGRATION.md "Ranks of rank-deficient trains")
         if os.environ.get("TTR_STRICT_RANKS", "1") == "0":
-            L.ttr_debug_set_knob(9, 0)
+            L.ttr_debug_set_knob(KNOB_RANK_NOISE_FLOOR, 0)
         # TTR_ORTH_SPLIT=<batch size>: ttr_orth_fixup's three-launch rounds from that batch size on (header: TTR_KNOB_ORTH_SPLIT)
         if os.environ.get("TTR_ORTH_SPLIT", "") != "":
-            L.ttr_debug_set_knob(15, int(os.environ["TTR_ORTH_SPLIT"]))
+            L.ttr_debug_set_knob(KNOB_ORTH_SPLIT, int(os.environ["TTR_ORTH_SPLIT"]))
         _lib = L
     return _lib
 
@@ -270,9 +121,9 @@ def lib():
 def _check(code: int, what: str):
     if code != 0:
         msg = lib().ttr_last_error().decode(errors="replace")
-        if code == -2:
+        if code == E_UNSUPPORTED:
             raise NotImplementedError(f"{what}: {msg}")
-        if code == -1:
+        if code == E_INVALID:
             raise ValueError(f"{what}: {msg}")
         raise RuntimeError(f"{what} failed ({code}): {msg}")
 
@@ -287,6 +138,21 @@ def dtype_code(dt: torch.dtype) -> int:
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _call(name: str, *args):
+    """Launch the entry point ``name`` (one whose last parameter is ``void* stream``) on the current stream and check its status."""
+    _check(getattr(lib(), name)(*args, _stream()), name)
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace(nbytes: int, device, floor: int = 0) -> Optional[torch.Tensor]:
+    """uint8 scratch of max(nbytes, floor) bytes, or None (the library then receives a null pointer) when that is 0."""
+    nbytes = max(nbytes, floor)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None
 
 
 def _first_cuda_tensor(args, kwargs):
@@ -379,15 +245,12 @@ def gemm(
         colscale = colscale.contiguous()
         cs_ptr, cs_stride = colscale.data_ptr(), colscale.shape[-1]
     wsb = L.ttr_gemm_workspace_bytes(dt, M, N, K, batch)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=A.device) if wsb > 0 else None
-    code = L.ttr_gemm(
-        dt, int(transA), int(transB), M, N, K,
-        A.data_ptr(), lda, sA, B.data_ptr(), ldb, sB, C.data_ptr(), N, M * N,
-        rs_ptr, rs_stride, rowscale_mode if rowscale is not None else SCALE_NONE,
-        cs_ptr, cs_stride, colscale_mode if colscale is not None else SCALE_NONE,
-        batch, ws.data_ptr() if ws is not None else None, wsb, _stream(),
-    )
-    _check(code, "ttr_gemm")
+    ws = _workspace(wsb, A.device)
+    _call("ttr_gemm", dt, int(transA), int(transB), M, N, K,
+          A.data_ptr(), lda, sA, B.data_ptr(), ldb, sB, C.data_ptr(), N, M * N,
+          rs_ptr, rs_stride, rowscale_mode if rowscale is not None else SCALE_NONE,
+          cs_ptr, cs_stride, colscale_mode if colscale is not None else SCALE_NONE,
+          batch, _ptr(ws), wsb)
     return C
 
 
@@ -409,13 +272,10 @@ def gemm_axpby(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, alpha: float, 
     if M == 0 or N == 0 or batch == 0:
         return C
     wsb = L.ttr_gemm_workspace_bytes(dt, M, N, K, batch)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=A.device) if wsb > 0 else None
-    code = L.ttr_gemm_axpby(
-        dt, int(transA), int(transB), M, N, K,
-        A.data_ptr(), lda, sA, B.data_ptr(), ldb, sB, C.data_ptr(), N, M * N,
-        float(alpha), float(beta), batch, ws.data_ptr() if ws is not None else None, wsb, _stream(),
-    )
-    _check(code, "ttr_gemm_axpby")
+    ws = _workspace(wsb, A.device)
+    _call("ttr_gemm_axpby", dt, int(transA), int(transB), M, N, K,
+          A.data_ptr(), lda, sA, B.data_ptr(), ldb, sB, C.data_ptr(), N, M * N,
+          float(alpha), float(beta), batch, _ptr(ws), wsb)
     return C
 
 
@@ -432,10 +292,8 @@ def qr(A: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     if batch == 0:
         return Q, R
     wsb = L.ttr_qr_workspace_bytes(dt, m, n, batch)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=A.device)
-    code = L.ttr_qr(dt, m, n, batch, A.data_ptr(), lda, sA, Q.data_ptr(), k, m * k, R.data_ptr(), n, k * n,
-                    ws.data_ptr(), wsb, _stream())
-    _check(code, "ttr_qr")
+    ws = _workspace(wsb, A.device, 16)
+    _call("ttr_qr", dt, m, n, batch, A.data_ptr(), lda, sA, Q.data_ptr(), k, m * k, R.data_ptr(), n, k * n, ws.data_ptr(), wsb)
     return Q, R
 
 
@@ -453,9 +311,9 @@ def qr_t(At: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     if batch == 0:
         return Qt, R
     wsb = L.ttr_qr_workspace_bytes(dt, m, n, batch)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=At.device)
-    _check(L.ttr_qr_t(dt, m, n, batch, At.data_ptr(), ldat, sAt, Qt.data_ptr(), m, k * m, R.data_ptr(), n, k * n,
-                      ws.data_ptr(), wsb, _stream()), "ttr_qr_t")
+    ws = _workspace(wsb, At.device, 16)
+    _call("ttr_qr_t", dt, m, n, batch, At.data_ptr(), ldat, sAt, Qt.data_ptr(), m, k * m, R.data_ptr(), n, k * n,
+          ws.data_ptr(), wsb)
     return Qt, R
 
 
@@ -489,15 +347,13 @@ def qr_factor(A: torch.Tensor, expo_acc: Optional[torch.Tensor] = None) -> QrFac
     k = min(m, n)
     R = torch.empty((batch, k, n), dtype=A.dtype, device=A.device)
     wsb = L.ttr_qr_workspace_bytes(dt, m, n, max(batch, 1))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=A.device)
+    ws = _workspace(wsb, A.device, 16)
     if batch > 0 and expo_acc is not None:
         assert expo_acc.dtype == torch.int32 and expo_acc.numel() == batch and expo_acc.is_contiguous()
-        code = L.ttr_qr_factor_expo(dt, m, n, batch, A.data_ptr(), lda, sA, R.data_ptr(), n, k * n, ws.data_ptr(), wsb,
-                                    expo_acc.data_ptr(), _stream())
-        _check(code, "ttr_qr_factor_expo")
+        _call("ttr_qr_factor_expo", dt, m, n, batch, A.data_ptr(), lda, sA, R.data_ptr(), n, k * n, ws.data_ptr(), wsb,
+              expo_acc.data_ptr())
     elif batch > 0:
-        code = L.ttr_qr_factor(dt, m, n, batch, A.data_ptr(), lda, sA, R.data_ptr(), n, k * n, ws.data_ptr(), wsb, _stream())
-        _check(code, "ttr_qr_factor")
+        _call("ttr_qr_factor", dt, m, n, batch, A.data_ptr(), lda, sA, R.data_ptr(), n, k * n, ws.data_ptr(), wsb)
     return QrFactors(ws, wsb, m, n, batch, A.dtype, R)
 
 
@@ -519,16 +375,14 @@ def qr_factor_pushed(Rm: torch.Tensor, core4: torch.Tensor, expo_acc: Optional[t
     kq = min(k * I, n)
     R = torch.empty((batch, kq, n), dtype=core4.dtype, device=core4.device)
     wsb = L.ttr_qr_pushed_workspace_bytes(dt, I, n, max(batch, 1))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=core4.device)
+    ws = _workspace(wsb, core4.device, 16)
     if batch > 0 and expo_acc is not None:
         assert expo_acc.dtype == torch.int32 and expo_acc.numel() == batch and expo_acc.is_contiguous()
-        code = L.ttr_qr_factor_pushed_expo(dt, k, Rin, I, n, batch, Rm.data_ptr(), ldrm, sRm, core4.data_ptr(), Rin * I * n,
-                                           R.data_ptr(), n, kq * n, ws.data_ptr(), wsb, expo_acc.data_ptr(), _stream())
-        _check(code, "ttr_qr_factor_pushed_expo")
+        _call("ttr_qr_factor_pushed_expo", dt, k, Rin, I, n, batch, Rm.data_ptr(), ldrm, sRm, core4.data_ptr(), Rin * I * n,
+              R.data_ptr(), n, kq * n, ws.data_ptr(), wsb, expo_acc.data_ptr())
     elif batch > 0:
-        code = L.ttr_qr_factor_pushed(dt, k, Rin, I, n, batch, Rm.data_ptr(), ldrm, sRm, core4.data_ptr(), Rin * I * n,
-                                      R.data_ptr(), n, kq * n, ws.data_ptr(), wsb, _stream())
-        _check(code, "ttr_qr_factor_pushed")
+        _call("ttr_qr_factor_pushed", dt, k, Rin, I, n, batch, Rm.data_ptr(), ldrm, sRm, core4.data_ptr(), Rin * I * n,
+              R.data_ptr(), n, kq * n, ws.data_ptr(), wsb)
     flags = None
     if batch > 0 and k == 64:
         off = int(L.ttr_qr_pushed_flag_offset(dt, I, n, batch))
@@ -552,12 +406,10 @@ def qr_factor_pushed_sum(Rm: torch.Tensor, a4: torch.Tensor, b4: torch.Tensor) -
     kq = min(k * I, n)
     R = torch.empty((batch, kq, n), dtype=a4.dtype, device=a4.device)
     wsb = L.ttr_qr_pushed_workspace_bytes(dt, I, n, max(batch, 1))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=a4.device)
+    ws = _workspace(wsb, a4.device, 16)
     if batch > 0:
-        code = L.ttr_qr_factor_pushed_sum(dt, k, I, batch, Rm.data_ptr(), ldrm, sRm, a4.data_ptr(), ra, ca, ra * I * ca,
-                                          b4.data_ptr(), rb, cb, rb * I * cb, R.data_ptr(), n, kq * n, ws.data_ptr(), wsb,
-                                          _stream())
-        _check(code, "ttr_qr_factor_pushed_sum")
+        _call("ttr_qr_factor_pushed_sum", dt, k, I, batch, Rm.data_ptr(), ldrm, sRm, a4.data_ptr(), ra, ca, ra * I * ca,
+              b4.data_ptr(), rb, cb, rb * I * cb, R.data_ptr(), n, kq * n, ws.data_ptr(), wsb)
     return QrFactors(ws, wsb, k * I, n, batch, a4.dtype, R, pushed=(k, I))
 
 
@@ -592,20 +444,15 @@ def qr_apply(f: QrFactors, C: Optional[torch.Tensor] = None, kcols: Optional[int
         parts = int(L.ttr_qr_apply_pushed_gram_parts(dt, k, I, f.n, kcols)) if want_gram else 0
         if parts > 0:
             G = torch.empty((f.batch, parts, k, k), dtype=f.dtype, device=f.ws.device)
-            code = L.ttr_qr_apply_pushed_gram(dt, k, I, f.n, f.batch, f.ws.data_ptr(), f.wsb, cptr, ldc, sC, kcols,
-                                              Out.data_ptr(), kcols, f.m * kcols, G.data_ptr(), _stream())
-            _check(code, "ttr_qr_apply_pushed_gram")
+            _call("ttr_qr_apply_pushed_gram", dt, k, I, f.n, f.batch, f.ws.data_ptr(), f.wsb, cptr, ldc, sC, kcols,
+                  Out.data_ptr(), kcols, f.m * kcols, G.data_ptr())
         else:
             # skip_zero_rows: the rows kk >= 32 of packed items (f.rows32) stay unwritten -- only for results that are read
             # through the rows32-aware kernels (rowgram / rotgram / project)
-            code = L.ttr_qr_apply_pushed(dt, k, I, f.n, f.batch, f.ws.data_ptr(), f.wsb, cptr, ldc, sC, kcols,
-                                         Out.data_ptr(), kcols, f.m * kcols, int(bool(skip_zero_rows and f.rows32 is not None)),
-                                         _stream())
-            _check(code, "ttr_qr_apply_pushed")
+            _call("ttr_qr_apply_pushed", dt, k, I, f.n, f.batch, f.ws.data_ptr(), f.wsb, cptr, ldc, sC, kcols, Out.data_ptr(),
+                  kcols, f.m * kcols, int(bool(skip_zero_rows and f.rows32 is not None)))
         return (Out, G) if want_gram else Out
-    code = L.ttr_qr_apply(dt, f.m, f.n, f.batch, f.ws.data_ptr(), f.wsb, cptr, ldc, sC, kcols,
-                          Out.data_ptr(), kcols, f.m * kcols, _stream())
-    _check(code, "ttr_qr_apply")
+    _call("ttr_qr_apply", dt, f.m, f.n, f.batch, f.ws.data_ptr(), f.wsb, cptr, ldc, sC, kcols, Out.data_ptr(), kcols, f.m * kcols)
     return (Out, G) if want_gram else Out
 
 
@@ -634,18 +481,11 @@ def eigh_trunc(
     if batch == 0:
         return V, sigma, info
     wsb = L.ttr_eigh_workspace_bytes(dt, n, batch)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=G.device) if wsb > 0 else None
+    ws = _workspace(wsb, G.device)
     rmax = int(min(max(int(rmax), 1), 2**31 - 1))
-    code = L.ttr_eigh_trunc(
-        dt, n, batch, G.data_ptr(), ldg, sG, gparts, sGp, V.data_ptr(), n, n * n, sigma.data_ptr(), n, info.data_ptr(),
-        eig_mode, int(bool(use_delta)), float(delta2),
-        delta2_dev.data_ptr() if delta2_dev is not None else None, rmax, int(abs_floor),
-        sweeps.data_ptr() if sweeps is not None else None,
-        skip_items.data_ptr() if skip_items is not None else None,
-        sigma_in.data_ptr() if sigma_in is not None else None, sigma_in.shape[-1] if sigma_in is not None else 0,
-        ws.data_ptr() if ws is not None else None, wsb, _stream(),
-    )
-    _check(code, "ttr_eigh_trunc")
+    _call("ttr_eigh_trunc", dt, n, batch, G.data_ptr(), ldg, sG, gparts, sGp, V.data_ptr(), n, n * n, sigma.data_ptr(), n,
+          info.data_ptr(), eig_mode, int(bool(use_delta)), float(delta2), _ptr(delta2_dev), rmax, int(abs_floor),
+          _ptr(sweeps), _ptr(skip_items), _ptr(sigma_in), sigma_in.shape[-1] if sigma_in is not None else 0, _ptr(ws), wsb)
     return V, sigma, info
 
 
@@ -660,7 +500,6 @@ def eigh_top(G: torch.Tensor, r: int, thr: float, need_all: bool = False) -> Tup
     sigma[b][:r], zeros beyond), the others the full decomposition of ``eigh_trunc(G, EIG_RAW, ..., abs_floor=SOLVER_TRIDIAG)``
     (flat[b] = 2 when its kept sigma pass ``spectrum_flat``'s batch-mode test, else 0).  ``need_all``: eps mode -- the top-r path only
     takes items whose every eigenpair it computes (zero-tail items under a cap >= 32); sigma / V are complete for every item."""
-    L = lib()
     dt = dtype_code(G.dtype)
     gparts, sGp = 1, 0
     if G.dim() == 4:
@@ -675,8 +514,8 @@ def eigh_top(G: torch.Tensor, r: int, thr: float, need_all: bool = False) -> Tup
     info = torch.empty((batch,), dtype=torch.int32, device=G.device)
     flat = torch.empty((batch,), dtype=torch.int32, device=G.device)
     if batch:
-        _check(L.ttr_eigh_top(dt, n, batch, G.data_ptr(), ldg, sG, gparts, sGp, V.data_ptr(), n, n * n, sigma.data_ptr(), n,
-                              info.data_ptr(), int(r), float(thr), flat.data_ptr(), int(bool(need_all)), _stream()), "ttr_eigh_top")
+        _call("ttr_eigh_top", dt, n, batch, G.data_ptr(), ldg, sG, gparts, sGp, V.data_ptr(), n, n * n, sigma.data_ptr(), n,
+              info.data_ptr(), int(r), float(thr), flat.data_ptr(), int(bool(need_all)))
     return V, sigma, info, flat
 
 
@@ -700,16 +539,15 @@ def eigh_topk(G: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor, torc
         return Z, lam, torch.empty((0,), dtype=G.dtype, device=G.device)
     wsb = L.ttr_tridiag_workspace_bytes(dt, n, batch)
     ws = torch.empty(wsb, dtype=torch.uint8, device=G.device)
-    _check(L.ttr_tridiag(dt, n, batch, A.data_ptr(), n, n * n, d.data_ptr(), e.data_ptr(), tau.data_ptr(), ws.data_ptr(), wsb, _stream()),
-           "ttr_tridiag")
+    _call("ttr_tridiag", dt, n, batch, A.data_ptr(), n, n * n, d.data_ptr(), e.data_ptr(), tau.data_ptr(), ws.data_ptr(), wsb)
     sb = L.ttr_eigsel_scratch_bytes(dt, n, batch)
     scratch = torch.empty(sb, dtype=torch.uint8, device=G.device)
-    _check(L.ttr_tri_eigsel(dt, n, batch, int(k), d.data_ptr(), e.data_ptr(), lam.data_ptr(), Z.data_ptr(), scratch.data_ptr(), sb,
-                            _stream()), "ttr_tri_eigsel")
+    _call("ttr_tri_eigsel", dt, n, batch, int(k), d.data_ptr(), e.data_ptr(), lam.data_ptr(), Z.data_ptr(),
+          scratch.data_ptr(), sb)
     Zq, R = qr(Z)
     rmin = torch.diagonal(R, dim1=1, dim2=2).abs().amin(dim=1)
     Zq = Zq.contiguous()
-    _check(L.ttr_tridiag_back(dt, n, batch, int(k), A.data_ptr(), n, n * n, tau.data_ptr(), Zq.data_ptr(), _stream()), "ttr_tridiag_back")
+    _call("ttr_tridiag_back", dt, n, batch, int(k), A.data_ptr(), n, n * n, tau.data_ptr(), Zq.data_ptr())
     return Zq, lam, rmin
 
 
@@ -748,7 +586,7 @@ def bj_sweeps(G: torch.Tensor, V: torch.Tensor, b: int, relative: bool, tol: flo
     state[Bt:].fill_(-1.0)
     gn = norm(G.reshape(Bt, -1)) if not relative else None
     W = torch.empty((Bt * npairs, w, w), dtype=G.dtype, device=G.device)
-    scratch = torch.empty(max(int(L.ttr_bj_scratch_bytes(dt, b, npairs, Bt)), 16), dtype=torch.uint8, device=G.device)
+    scratch = _workspace(int(L.ttr_bj_scratch_bytes(dt, b, npairs, Bt)), G.device, 16)
     st = _stream()
     rounds = nbk - 1
     tranche = 8   # sweeps enqueued before the convergence word is looked at (one readback: control flow only).  Convergence
@@ -764,15 +602,14 @@ def bj_sweeps(G: torch.Tensor, V: torch.Tensor, b: int, relative: bool, tol: flo
             off = state.data_ptr() if (not relative and r == rounds - 1) else None
             _check(L.ttr_bj_apply(dt, b, npairs, Bt, G.data_ptr(), n, n * n, V.data_ptr(), n, n * n, tab, W.data_ptr(),
                                   ctrl.data_ptr(), off, st), "ttr_bj_apply")
-        _check(L.ttr_bj_control(dt, Bt, ctrl.data_ptr(), state.data_ptr(), gn.data_ptr() if gn is not None else None,
-                                int(relative), float(tol), st), "ttr_bj_control")
+        _check(L.ttr_bj_control(dt, Bt, ctrl.data_ptr(), state.data_ptr(), _ptr(gn), int(relative), float(tol), st),
+               "ttr_bj_control")
     return ctrl
 
 
 @_on_device
 def norm(x: torch.Tensor) -> torch.Tensor:
     """Frobenius norm per batch item of a [batch, ...] tensor -> [batch]."""
-    L = lib()
     dt = dtype_code(x.dtype)
     x = x.contiguous()
     batch = x.shape[0]
@@ -789,14 +626,13 @@ def norm(x: torch.Tensor) -> torch.Tensor:
         if k > 1:
             part = norm(x.reshape(batch * k, count // k))
             return norm(part.reshape(batch, k))
-    _check(L.ttr_norm(dt, count, batch, x.data_ptr(), count, out.data_ptr(), _stream()), "ttr_norm")
+    _call("ttr_norm", dt, count, batch, x.data_ptr(), count, out.data_ptr())
     return out
 
 
 @_on_device
 def scale_cols(X: torch.Tensor, s: torch.Tensor, mode: int) -> torch.Tensor:
     """out[b, i, j] = X[b, i, j] * s[b, j] (SCALE_MUL) or / s[b, j] (SCALE_DIV)."""
-    L = lib()
     dt = dtype_code(X.dtype)
     X, ldx, sX = _mat(X)
     s = s.contiguous()
@@ -804,9 +640,8 @@ def scale_cols(X: torch.Tensor, s: torch.Tensor, mode: int) -> torch.Tensor:
     out = torch.empty((batch, rows, cols), dtype=X.dtype, device=X.device)
     if out.numel() == 0:
         return out
-    code = L.ttr_scale_cols(dt, rows, cols, batch, X.data_ptr(), ldx, sX, s.data_ptr(), s.shape[-1], mode,
-                            out.data_ptr(), cols, rows * cols, _stream())
-    _check(code, "ttr_scale_cols")
+    _call("ttr_scale_cols", dt, rows, cols, batch, X.data_ptr(), ldx, sX, s.data_ptr(), s.shape[-1], mode,
+          out.data_ptr(), cols, rows * cols)
     return out
 
 
@@ -815,8 +650,7 @@ def mask_cols(X: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
     """In place: X[b, :, j] = 0 for j >= keep[b] (keep: int32 [batch] on the device)."""
     X3, ldx, sX = _mat(X)
     assert X3.data_ptr() == X.data_ptr() and keep.dtype == torch.int32 and keep.shape[0] == X.shape[0]
-    _check(lib().ttr_mask_cols(dtype_code(X.dtype), X.shape[1], X.shape[2], X.shape[0], X.data_ptr(), ldx, sX, keep.data_ptr(),
-                               _stream()), "ttr_mask_cols")
+    _call("ttr_mask_cols", dtype_code(X.dtype), X.shape[1], X.shape[2], X.shape[0], X.data_ptr(), ldx, sX, keep.data_ptr())
     return X
 
 
@@ -834,11 +668,8 @@ def spectrum_flat(sigma: torch.Tensor, keep: int, thr: float, use_delta: bool = 
     batch, n = sigma.shape
     flat = torch.empty((batch,), dtype=torch.int32, device=sigma.device)
     if batch:
-        _check(lib().ttr_spectrum_flat(dtype_code(sigma.dtype), n, batch, sigma.data_ptr(), n, int(keep), float(thr),
-                                       int(bool(use_delta)), float(delta2),
-                                       delta2_dev.data_ptr() if delta2_dev is not None else None,
-                                       flat.data_ptr(), rows32.data_ptr() if rows32 is not None else None, _stream()),
-               "ttr_spectrum_flat")
+        _call("ttr_spectrum_flat", dtype_code(sigma.dtype), n, batch, sigma.data_ptr(), n, int(keep), float(thr),
+              int(bool(use_delta)), float(delta2), _ptr(delta2_dev), flat.data_ptr(), _ptr(rows32))
     return flat
 
 
@@ -856,15 +687,12 @@ def rowgram(M: torch.Tensor, V1: Optional[torch.Tensor] = None, skip: Optional[t
     if batch == 0:
         return G
     if V1 is None:
-        _check(L.ttr_rowgram(dt, R, n, batch, M.data_ptr(), ldm, sM, G.data_ptr(), parts,
-                             rows32.data_ptr() if rows32 is not None else None, _stream()), "ttr_rowgram")
+        _call("ttr_rowgram", dt, R, n, batch, M.data_ptr(), ldm, sM, G.data_ptr(), parts, _ptr(rows32))
     else:
         V1, ldv, sV = _mat(V1)
         assert V1.shape == (batch, R, R)
-        _check(L.ttr_rotgram(dt, R, n, batch, M.data_ptr(), ldm, sM, V1.data_ptr(), ldv, sV, G.data_ptr(), parts,
-                             skip.data_ptr() if skip is not None else None,
-                             rows32.data_ptr() if rows32 is not None else None, _stream()),
-               "ttr_rotgram")
+        _call("ttr_rotgram", dt, R, n, batch, M.data_ptr(), ldm, sM, V1.data_ptr(), ldv, sV, G.data_ptr(), parts, _ptr(skip),
+              _ptr(rows32))
     return G
 
 
@@ -874,7 +702,6 @@ def project(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, sigma
             rows32: Optional[torch.Tensor] = None):
     """right [batch, ro, n] = diag(1/sigma) U^T M and left [batch, R, ro] = U diag(sigma) with U = V1 V2[:, :ro]
     (ttr_project; ``scale_right=False``: right = U^T M, left = U).  ``out``: optional contiguous destination of right."""
-    L = lib()
     dt = dtype_code(M.dtype)
     M, ldm, sM = _mat(M)
     batch, R, n = M.shape
@@ -895,10 +722,8 @@ def project(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, sigma
     if sigma is not None:
         sigma = sigma.contiguous()
         sp, ss = sigma.data_ptr(), sigma.shape[-1]
-    _check(L.ttr_project(dt, R, n, ro, batch, M.data_ptr(), ldm, sM, v1p, ldv1, sV1, V2.data_ptr(), ldv2, sV2, sp, ss,
-                         int(bool(scale_right)), right.data_ptr(), n, ro * n,
-                         left.data_ptr() if left is not None else None, ro, R * ro,
-                         rows32.data_ptr() if rows32 is not None else None, _stream()), "ttr_project")
+    _call("ttr_project", dt, R, n, ro, batch, M.data_ptr(), ldm, sM, v1p, ldv1, sV1, V2.data_ptr(), ldv2, sV2, sp, ss,
+          int(bool(scale_right)), right.data_ptr(), n, ro * n, _ptr(left), ro, R * ro, _ptr(rows32))
     return right, left
 
 
@@ -918,15 +743,13 @@ def colgram(M: torch.Tensor, V1: Optional[torch.Tensor] = None, skip: Optional[t
     if batch == 0:
         return G
     wsb = L.ttr_colgram_workspace_bytes(dt, rows, n, batch)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=M.device) if wsb > 0 else None
+    ws = _workspace(wsb, M.device)
     v1p, ldv, sV = None, 0, 0
     if V1 is not None:
         V1, ldv, sV = _mat(V1)
         assert V1.shape == (batch, n, n)
         v1p = V1.data_ptr()
-    _check(L.ttr_colgram(dt, rows, n, batch, M.data_ptr(), ldm, sM, v1p, ldv, sV, G.data_ptr(),
-                         ws.data_ptr() if ws is not None else None, wsb, skip.data_ptr() if skip is not None else None,
-                         _stream()), "ttr_colgram")
+    _call("ttr_colgram", dt, rows, n, batch, M.data_ptr(), ldm, sM, v1p, ldv, sV, G.data_ptr(), _ptr(ws), wsb, _ptr(skip))
     return G
 
 
@@ -936,7 +759,6 @@ def colproject(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, si
     """left [batch, rows, ro] = M U [/ sigma], right [batch, ro, n] = [sigma] U^T with U = V1 V2[:, :ro] (ttr_colproject).
     ``left_out``: optional contiguous [batch, rows, ro] destination of ``left`` (may lie in M's own storage BELOW the rows this
     call reads: the in-place first step of a config-scale dense TT-SVD, ``_hipops._colproject_inplace``)."""
-    L = lib()
     dt = dtype_code(M.dtype)
     M, ldm, sM = _mat(M)
     batch, rows, n = M.shape
@@ -962,9 +784,8 @@ def colproject(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, si
     if sigma is not None:
         sigma = sigma.contiguous()
         sp, ss = sigma.data_ptr(), sigma.shape[-1]
-    _check(L.ttr_colproject(dt, rows, n, ro, batch, M.data_ptr(), ldm, sM, v1p, ldv1, sV1, V2.data_ptr(), ldv2, sV2, sp, ss,
-                            int(bool(left_ortho)), left.data_ptr(), ro, rows * ro, right.data_ptr(), n, ro * n, _stream()),
-           "ttr_colproject")
+    _call("ttr_colproject", dt, rows, n, ro, batch, M.data_ptr(), ldm, sM, v1p, ldv1, sV1, V2.data_ptr(), ldv2, sV2, sp, ss,
+          int(bool(left_ortho)), left.data_ptr(), ro, rows * ro, right.data_ptr(), n, ro * n)
     return left, right
 
 
@@ -972,7 +793,6 @@ def colproject(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, si
 def pow2_normalize(x: torch.Tensor, expo_acc: Optional[torch.Tensor] = None, exponent_only: bool = False):
     """[batch, ...] -> (x * 2^-e per batch item, e int32 [batch]) with e the binary exponent of ||x[b]||;
     ``expo_acc`` (int32 [batch]) is incremented by e in place.  ``exponent_only``: returns (None, e), x is only read."""
-    L = lib()
     dt = dtype_code(x.dtype)
     x = x.contiguous()
     batch = x.shape[0]
@@ -981,9 +801,7 @@ def pow2_normalize(x: torch.Tensor, expo_acc: Optional[torch.Tensor] = None, exp
     e = torch.empty((batch,), dtype=torch.int32, device=x.device)   # (every entry is written by the kernel)
     if batch == 0:
         return out, e
-    _check(L.ttr_pow2_normalize(dt, count, batch, x.data_ptr(), count, out.data_ptr() if out is not None else None, count,
-                                e.data_ptr(), expo_acc.data_ptr() if expo_acc is not None else None, _stream()),
-           "ttr_pow2_normalize")
+    _call("ttr_pow2_normalize", dt, count, batch, x.data_ptr(), count, _ptr(out), count, e.data_ptr(), _ptr(expo_acc))
     return out, e
 
 
@@ -991,7 +809,6 @@ def pow2_normalize(x: torch.Tensor, expo_acc: Optional[torch.Tensor] = None, exp
 def scale_batch(x: torch.Tensor, scale=None, expo: Optional[torch.Tensor] = None, expo_sign: int = 1) -> torch.Tensor:
     """out[b] = x[b] * scale[b] * 2^(expo_sign * expo[b]) for a [batch, ...] tensor.  ``scale``: None, a python
     number (one scalar for the whole batch) or a [batch] tensor; ``expo``: None or int32 [batch]."""
-    L = lib()
     dt = dtype_code(x.dtype)
     x = x.contiguous()
     batch = x.shape[0]
@@ -1008,9 +825,7 @@ def scale_batch(x: torch.Tensor, scale=None, expo: Optional[torch.Tensor] = None
             scale = scale.to(x.dtype).contiguous()
             ss = 1
         sp = scale.data_ptr()
-    _check(L.ttr_scale_batch(dt, count, batch, x.data_ptr(), count, sp, ss,
-                             expo.data_ptr() if expo is not None else None, int(expo_sign),
-                             out.data_ptr(), count, _stream()), "ttr_scale_batch")
+    _call("ttr_scale_batch", dt, count, batch, x.data_ptr(), count, sp, ss, _ptr(expo), int(expo_sign), out.data_ptr(), count)
     return out
 
 
@@ -1018,14 +833,12 @@ def scale_batch(x: torch.Tensor, scale=None, expo: Optional[torch.Tensor] = None
 def carry_rows32(R: torch.Tensor) -> torch.Tensor:
     """[batch, 64, cols] -> int32 [batch]: 1 where rows 32.. of R[b] are negligible by the packing test of the fused push
     (ttr_carry_rows32): the `rows32` flags of a carry that no ``qr_factor_pushed`` follows (the sweep's last core)."""
-    L = lib()
     R, ldr, sR = _mat(R)
     batch, rows, cols = R.shape
     assert rows == 64
     flag = torch.empty((batch,), dtype=torch.int32, device=R.device)
     if batch:
-        _check(L.ttr_carry_rows32(dtype_code(R.dtype), cols, batch, R.data_ptr(), ldr, sR, flag.data_ptr(), _stream()),
-               "ttr_carry_rows32")
+        _call("ttr_carry_rows32", dtype_code(R.dtype), cols, batch, R.data_ptr(), ldr, sR, flag.data_ptr())
     return flag
 
 
@@ -1047,17 +860,14 @@ def orth_fixup(X: torch.Tensor, sigma: torch.Tensor, r: int, dead_rel: float, co
     if batch == 0 or r == 0 or n == 0:
         return
     wsb = int(L.ttr_orth_fixup_workspace_bytes(dt, r, n, batch, es))   # > 0: a large batch, three launches per round
-    ws = torch.empty(wsb, dtype=torch.uint8, device=X.device) if wsb > 0 else None
-    _check(L.ttr_orth_fixup(dt, r, n, batch, X.data_ptr(), vs, es, X.shape[1] * X.shape[2], sigma.data_ptr(),
-                            sigma.shape[-1], float(dead_rel), rank_dev.data_ptr() if rank_dev is not None else None,
-                            ws.data_ptr() if ws is not None else None, wsb, _stream()),
-           "ttr_orth_fixup")
+    ws = _workspace(wsb, X.device)
+    _call("ttr_orth_fixup", dt, r, n, batch, X.data_ptr(), vs, es, X.shape[1] * X.shape[2], sigma.data_ptr(), sigma.shape[-1],
+          float(dead_rel), _ptr(rank_dev), _ptr(ws), wsb)
 
 
 @_on_device
 def krp_contract(T: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     """out[p, q, r] = sum_j T[p, j, q, r] * B[j, r] for contiguous T [P, J, Q, R], B [J, R]."""
-    L = lib()
     dt = dtype_code(T.dtype)
     assert T.dim() == 4 and B.dim() == 2 and T.is_cuda and T.dtype == B.dtype
     P, J, Q, R = T.shape
@@ -1065,33 +875,30 @@ def krp_contract(T: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     T = T.contiguous()
     B = B.contiguous()
     out = torch.empty((P, Q, R), dtype=T.dtype, device=T.device)
-    code = L.ttr_krp_contract(dt, P, J, Q, R, T.data_ptr(), B.data_ptr(), R, out.data_ptr(), _stream())
-    _check(code, "ttr_krp_contract")
+    _call("ttr_krp_contract", dt, P, J, Q, R, T.data_ptr(), B.data_ptr(), R, out.data_ptr())
     return out
 
 
 @_on_device
 def hadamard(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    L = lib()
     dt = dtype_code(a.dtype)
     assert a.shape == b.shape and a.dtype == b.dtype and a.is_cuda
     a, b = a.contiguous(), b.contiguous()
     out = torch.empty_like(a)
-    _check(L.ttr_hadamard(dt, a.numel(), a.data_ptr(), b.data_ptr(), out.data_ptr(), _stream()), "ttr_hadamard")
+    _call("ttr_hadamard", dt, a.numel(), a.data_ptr(), b.data_ptr(), out.data_ptr())
     return out
 
 
 @_on_device
 def core_kron(a: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     """[B, R1, I, R2] (x) [B, S1, I, S2] -> [B, R1*S1, I, R2*S2] (slice-wise Kronecker product)."""
-    L = lib()
     dt = dtype_code(a.dtype)
     assert a.dim() == 4 and c.dim() == 4 and a.dtype == c.dtype and a.shape[0] == c.shape[0] and a.shape[2] == c.shape[2]
     a, c = a.contiguous(), c.contiguous()
     B, R1, I, R2 = a.shape
     _, S1, _, S2 = c.shape
     out = torch.empty((B, R1 * S1, I, R2 * S2), dtype=a.dtype, device=a.device)
-    _check(L.ttr_core_kron(dt, B, R1, S1, I, R2, S2, a.data_ptr(), c.data_ptr(), out.data_ptr(), _stream()), "ttr_core_kron")
+    _call("ttr_core_kron", dt, B, R1, S1, I, R2, S2, a.data_ptr(), c.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1126,11 +933,10 @@ def gather_chain(cores, idx, out: Optional[torch.Tensor] = None, direct_max_poin
     wsb = L.ttr_gather_chain_workspace_bytes(dt, n, ranks, sizes, P, B)
     if wsb < 0:
         raise ValueError("ttr_gather_chain_workspace_bytes: bad arguments")
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(wsb, dev, 1)
     flag = torch.empty(1, dtype=torch.int32, device=dev)
-    _check(L.ttr_gather_chain(dt, n, B, P, ranks, sizes, ptrs, strides, 1 if idx[0].dtype == torch.int64 else 0, iptrs, istr,
-                              out.data_ptr(), *[int(s) for s in out.stride()], int(direct_max_points), flag.data_ptr(),
-                              ws.data_ptr(), wsb, _stream()), "ttr_gather_chain")
+    _call("ttr_gather_chain", dt, n, B, P, ranks, sizes, ptrs, strides, 1 if idx[0].dtype == torch.int64 else 0, iptrs, istr,
+          out.data_ptr(), *[int(s) for s in out.stride()], int(direct_max_points), flag.data_ptr(), ws.data_ptr(), wsb)
     if int(flag.item()):  # the one host read of the call
         raise IndexError("index out of range: an index array entry lies outside its mode")
     return out
@@ -1143,7 +949,6 @@ def gather_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tensor, 
     strides), int64 device vectors ``xrow`` (or None: X[p]) and ``idx`` of length P -> Y [P, rn].  ``idx`` wraps negative values
     (-I <= idx < I); ``xrow`` does not (0 <= xrow < rows).  Nothing is read back: an out-of-range entry sets the device word
     ``flag`` (allocated when not given) and leaves Y unwritten."""
-    L = lib()
     dt = dtype_code(X.dtype)
     assert X.dim() == 2 and G.dim() == 3 and X.dtype == G.dtype and X.shape[1] == G.shape[0]
     if X.shape[1] > 1 and X.stride(1) != 1:
@@ -1161,9 +966,8 @@ def gather_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tensor, 
         flag = torch.empty(1, dtype=torch.int32, device=X.device)
     ldx = int(X.stride(0)) if X.shape[0] > 1 else int(r)
     ldy = int(out.stride(0)) if P > 1 else int(rn)
-    _check(L.ttr_gather_step(dt, P, X.shape[0], r, rn, I, X.data_ptr(), ldx, xrow.data_ptr() if xrow is not None else None,
-                             G.data_ptr(), *[int(s) for s in G.stride()], idx.data_ptr(), out.data_ptr(), ldy, flag.data_ptr(),
-                             _stream()), "ttr_gather_step")
+    _call("ttr_gather_step", dt, P, X.shape[0], r, rn, I, X.data_ptr(), ldx, _ptr(xrow), G.data_ptr(),
+          *[int(s) for s in G.stride()], idx.data_ptr(), out.data_ptr(), ldy, flag.data_ptr())
     return out
 
 
@@ -1183,8 +987,8 @@ def maxvol(A: torch.Tensor, tol: float, max_iters: int, status: Optional[torch.T
     ws = torch.empty(wsb, dtype=torch.uint8, device=A.device)
     if status is not None:
         assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2 * B
-    _check(L.ttr_maxvol(dt, B, N, r, A.data_ptr(), N * r, float(tol), int(max_iters), index.data_ptr(), C.data_ptr(), N * r,
-                        status.data_ptr() if status is not None else None, ws.data_ptr(), wsb, _stream()), "ttr_maxvol")
+    _call("ttr_maxvol", dt, B, N, r, A.data_ptr(), N * r, float(tol), int(max_iters), index.data_ptr(), C.data_ptr(), N * r,
+          _ptr(status), ws.data_ptr(), wsb)
     return index, C
 
 
@@ -1216,9 +1020,9 @@ def als_normal(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: t
     K = r0 * r1
     Gp = torch.empty((T, K, K), dtype=L.dtype, device=L.device)
     hp = torch.empty((T, K), dtype=L.dtype, device=L.device)
-    _check(lib().ttr_als_normal(dt, T, r0, r1, L.data_ptr(), ldl, R.data_ptr(), ldr, w.data_ptr() if w is not None else None,
-                                y.data_ptr(), perm.contiguous().data_ptr(), task_begin.contiguous().data_ptr(),
-                                task_end.contiguous().data_ptr(), Gp.data_ptr(), hp.data_ptr(), _stream()), "ttr_als_normal")
+    _call("ttr_als_normal", dt, T, r0, r1, L.data_ptr(), ldl, R.data_ptr(), ldr, _ptr(w), y.data_ptr(),
+          perm.contiguous().data_ptr(), task_begin.contiguous().data_ptr(), task_end.contiguous().data_ptr(),
+          Gp.data_ptr(), hp.data_ptr())
     return Gp, hp
 
 
@@ -1241,9 +1045,8 @@ def spd_solve(Gp: torch.Tensor, hp: torch.Tensor, part_off: torch.Tensor, part_b
     assert status.dtype == torch.int32 and status.is_contiguous() and status.shape[0] == n and X.shape[0] == n
     if counts is not None:
         assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape[0] == n
-    _check(lib().ttr_spd_solve(dt, n, K, Gp.data_ptr(), hp.data_ptr(), part_off.data_ptr(), int(part_base), X.data_ptr(),
-                               *_xout(X, inner), Gsum.data_ptr(), hsum.data_ptr(), status.data_ptr(),
-                               counts.data_ptr() if counts is not None else None, _stream()), "ttr_spd_solve")
+    _call("ttr_spd_solve", dt, n, K, Gp.data_ptr(), hp.data_ptr(), part_off.data_ptr(), int(part_base), X.data_ptr(),
+          *_xout(X, inner), Gsum.data_ptr(), hsum.data_ptr(), status.data_ptr(), _ptr(counts))
 
 
 @_on_device
@@ -1252,31 +1055,10 @@ def pinv_finish(V: torch.Tensor, sigma: torch.Tensor, t: torch.Tensor, status: t
     dt = dtype_code(V.dtype)
     n, K = int(V.shape[0]), int(V.shape[-1])
     assert V.is_contiguous() and sigma.is_contiguous() and t.is_contiguous() and t.numel() == n * K
-    _check(lib().ttr_pinv_finish(dt, n, K, V.data_ptr(), sigma.data_ptr(), t.data_ptr(), status.data_ptr(), X.data_ptr(),
-                                 *_xout(X, inner), _stream()), "ttr_pinv_finish")
+    _call("ttr_pinv_finish", dt, n, K, V.data_ptr(), sigma.data_ptr(), t.data_ptr(), status.data_ptr(), X.data_ptr(),
+          *_xout(X, inner))
 
 
-KNOB_QR_PANEL = 0
-KNOB_BJ_INNER_SWEEPS = 1
-KNOB_GEMM_BIG = 2
-KNOB_QR_STAMP_BX, KNOB_QR_STAMP_BY = 3, 4
-KNOB_QR_F64_NW4 = 5
-KNOB_QR_RANK_SKIP = 6
-KNOB_QR_PACK = 7
-KNOB_EIGH_SMALL = 8
-KNOB_RANK_NOISE_FLOOR = 9
-KNOB_QR_STAGGER = 16
-KNOB_QR_PACK_PRE = 17
-KNOB_EIGH_BIG_OCC = 18
-KNOB_ORTH_ROUNDS = 10
-KNOB_JACOBI_LIVE_WAVE = 11
-KNOB_ORTH_V2 = 12
-KNOB_QR_INTERLEAVE = 13
-KNOB_SWEEP_STAGGER = 14
-KNOB_ORTH_SPLIT = 15
-
-
-ALG_SVD, ALG_EIG = 0, 1
 RANK_NONE = 2**31 - 1   # rank cap meaning "none" (round.py:83-84)
 
 
@@ -1300,11 +1082,9 @@ def round_tt_sweep(cores, rcap, algorithm: str, eps_mode: bool, eps: float, flat
     rc = (c_int64 * max(N - 1, 1))(*[int(r) for r in rcap])
     cin = (c_void_p * N)(*[c.data_ptr() for c in cores])
     cout = (c_void_p * N)(*[o.data_ptr() for o in outs])
-    code = lib().ttr_round_tt(dtype_code(cores[0].dtype), N, sh, B, cin, rc, ALG_SVD if algorithm == "svd" else ALG_EIG,
-                              int(bool(eps_mode)), float(eps), float(flat_thr), int(bool(use_eigh_top)), cout,
-                              ranks_dev.data_ptr() if ranks_dev is not None else None,
-                              zero_flag.data_ptr() if zero_flag is not None else None, ws.data_ptr(), ws.numel(), _stream())
-    _check(code, "ttr_round_tt")
+    _call("ttr_round_tt", dtype_code(cores[0].dtype), N, sh, B, cin, rc, ALG_SVD if algorithm == "svd" else ALG_EIG,
+          int(bool(eps_mode)), float(eps), float(flat_thr), int(bool(use_eigh_top)), cout, _ptr(ranks_dev), _ptr(zero_flag),
+          ws.data_ptr(), ws.numel())
 
 
 def set_knob(knob: int, value: int):
