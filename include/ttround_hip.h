@@ -53,9 +53,9 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
-#define TTR_ABI_VERSION 14
+#define TTR_ABI_VERSION 15
 int ttr_version(void);
 const char* ttr_last_error(void);
 
@@ -765,6 +765,64 @@ int ttr_spd_solve(int dtype, int64_t n_items, int64_t K, const void* Gp, const v
                   const void* counts, void* stream);
 int ttr_pinv_finish(int dtype, int64_t n_items, int64_t K, const void* V, const void* sigma, const void* t, const void* status,
                     void* X, int64_t inner, int64_t s_item, int64_t s_a, int64_t s_b, void* stream);
+
+/*
+ * Sparse TT-SVD from samples (ABI 15; interpolation.py:122-218, `sparse_tt_svd`): the TT-SVD of the tensor that holds P samples
+ * y at the integer positions X [P, N] and zeros elsewhere.  The reference scatters the samples of every step into a dense
+ * nrows x ncols matrix D (`sparse_covariance`, `full_times_sparse`; ncols = the number of distinct index suffixes, ~P for sparse
+ * data) and multiplies it; these entries work on the samples themselves and never build D.
+ *
+ * Canonical order (once per decomposition).  ttr_sparse_keys validates X (int64, element strides sx0 / sx1) against `shape`
+ * (device int64 [N]): the int32 word at `flag` is set to 0, then bit 0 is set when an index lies outside [0, shape[n]); when it
+ * is set nothing else is written.  Otherwise key[p] = ((x_N I_{N-1} + x_{N-1}) ...) I_1 + x_1 (x_N the major key; the caller
+ * guarantees prod(shape) < 2^63; key = NULL: validation only).  The caller sorts the keys (any device sort) and passes the
+ * sorting permutation (int32 [P]; P < 2^31) to ttr_sparse_levels: lev[p] (int32) = the deepest mode, 1-based, in which sorted sample p differs from
+ * sorted sample p - 1 (N for p = 0); a repeated position gets 0 and sets bit 1 of `flag` (which this entry does not clear;
+ * with bit 0 set it writes nothing).  In this order the columns of EVERY step n -- the distinct suffixes x_{n+1..N} -- are
+ * contiguous runs that start where lev >= n + 1, and inside a run the entries ascend in x_n: nothing is sorted again.
+ *
+ * The unfolding of a step is a block table: column c owns the blocks colptr[c] .. colptr[c + 1) (int32 [C + 1]), block b sits
+ * at mode index blk_i[b] (int32, ascending inside a column, each at most once) and carries r values V[b * ldv + a] -- rows
+ * a * I + blk_i[b] of column c of D.  (Step 1: the blocks are the sorted samples, r = 1; after a step, its columns with the q
+ * projected values are the next step's blocks.)
+ *
+ * ttr_sparse_gram   G (n x n, n = r I, leading dimension ldg) = D D^T:
+ *                       G[a I + i][b I + j] = sum over the columns c that hold both i and j of V_ci[a] V_cj[b].
+ *                   `blkcol` (int32 [nb]): the column of every block; `ilist` (int32 [nb]): the blocks grouped by mode index,
+ *                   ascending block number within a group (a stable sort of blk_i); `iptr` (int32 [I + 1]): the groups.
+ *                   A workgroup owns one i, a range of j >= i and a tile of (a, b); it walks the blocks of i in list order and,
+ *                   for each, the partner blocks of that block's column inside its j range: sum_c m_c^2 r^2 / 2 multiply-adds
+ *                   (m_c = blocks of column c).  Every element is one thread's fma chain in ascending column order; a long i
+ *                   list is split into ttr_sparse_gram_parts(...) parts whose partial matrices (in `workspace`,
+ *                   ttr_sparse_gram_workspace_bytes) are summed in part order; j < i is mirrored.  No floating-point atomics:
+ *                   G is exactly symmetric and bit-identical from run to run; rows / columns of a mode index that never occurs
+ *                   are exact zeros.  r I <= ttr_eigh_max_n(dtype).
+ * ttr_sparse_project W[c * ldw + k] = sum over the blocks b of column c, ascending, and a = 0 .. r-1 of
+ *                       V[b][a] * U[(a I + blk_i[b]) * su_row + k * su_col],    k = 0 .. q-1
+ *                   i.e. W[c] = sum_b V_b @ core[:, blk_i[b], :] with core = U[:, :q] viewed as [r, I, q]: the gather step of
+ *                   ttr_gather_step fused with the segmented sum over a column, `core` read from the eigenvector matrix where
+ *                   it lies.  W [C, q] is the next step's V.
+ * ttr_sparse_group  the blocks grouped by mode index, for ttr_sparse_gram: ilist (int32 [nb]) = a STABLE counting sort of the block
+ *                   numbers by blk_i (chunk histograms in LDS, one scan, a ranked scatter: the device sort idiom of
+ *                   ttr_gather_chain), iptr (int32 [I + 1]) = the group offsets.  I <= 4096.  Workspace:
+ *                   ttr_sparse_group_workspace_bytes.  Entries of blk_i outside [0, I) are left out.
+ * All index arrays are bounds-checked where they are used as addresses (out-of-range entries are skipped).
+ */
+int ttr_sparse_keys(int64_t P, int64_t N, const void* X, int64_t sx0, int64_t sx1, const void* shape, void* key, void* flag,
+                    void* stream);
+int ttr_sparse_levels(int64_t P, int64_t N, const void* X, int64_t sx0, int64_t sx1, const void* perm, void* lev, void* flag,
+                      void* stream);
+int64_t ttr_sparse_group_workspace_bytes(int64_t nb, int64_t I);
+int ttr_sparse_group(int64_t nb, int64_t I, const void* blk_i, void* ilist, void* iptr, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int64_t ttr_sparse_gram_parts(int dtype, int64_t r, int64_t I, int64_t nb);
+int64_t ttr_sparse_gram_workspace_bytes(int dtype, int64_t r, int64_t I, int64_t nb);
+int ttr_sparse_gram(int dtype, int64_t r, int64_t I, int64_t nb, int64_t C, const void* colptr, const void* blk_i,
+                    const void* blkcol, const void* ilist, const void* iptr, const void* V, int64_t ldv, void* G, int64_t ldg,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int ttr_sparse_project(int dtype, int64_t r, int64_t I, int64_t q, int64_t nb, int64_t C, const void* colptr, const void* blk_i,
+                       const void* V, int64_t ldv, const void* U, int64_t su_row, int64_t su_col, void* W, int64_t ldw,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -1112,3 +1112,93 @@ def prof_collect():
     cnt = (c_int64 * n)()
     lib().ttr_prof_collect(ms, cnt)
     return {k: {"ms": ms[i], "launches": cnt[i]} for i, k in enumerate(PROF_KINDS)}
+
+
+# ---------------------------------------------------------------------------------------------- sparse TT-SVD (ttr_sparse.hip)
+@_on_device
+def sparse_keys(X: torch.Tensor, shape_dev: torch.Tensor, flag: torch.Tensor, want_keys: bool = True) -> Optional[torch.Tensor]:
+    """ttr_sparse_keys: validate X [P, N] (int64) against ``shape_dev`` (int64 [N], device) into ``flag`` (int32 [1], bit 0) and
+    return the linear sort keys (x_N major, x_1 minor), or None with ``want_keys=False`` (validation only).  Nothing is read back."""
+    assert X.dim() == 2 and X.dtype == torch.int64 and shape_dev.dtype == torch.int64 and flag.dtype == torch.int32
+    P, N = X.shape
+    key = torch.empty(P, dtype=torch.int64, device=X.device) if want_keys else None
+    _call("ttr_sparse_keys", P, N, X.data_ptr(), int(X.stride(0)), int(X.stride(1)), shape_dev.data_ptr(), _ptr(key),
+          flag.data_ptr())
+    return key
+
+
+@_on_device
+def sparse_levels(X: torch.Tensor, perm: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
+    """ttr_sparse_levels: int32 [P], the deepest mode (1-based) in which sample perm[p] differs from sample perm[p - 1] (N for
+    p = 0, 0 and bit 1 of ``flag`` for a repeated position)."""
+    assert X.dim() == 2 and X.dtype == torch.int64 and perm.dtype == torch.int32 and perm.is_contiguous()
+    P, N = X.shape
+    lev = torch.empty(P, dtype=torch.int32, device=X.device)
+    _call("ttr_sparse_levels", P, N, X.data_ptr(), int(X.stride(0)), int(X.stride(1)), perm.data_ptr(), lev.data_ptr(),
+          flag.data_ptr())
+    return lev
+
+
+@_on_device
+def sparse_group(blk_i: torch.Tensor, I: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ttr_sparse_group: (ilist int32 [nb], iptr int32 [I + 1]) -- the block numbers grouped by mode index ``blk_i`` (int32
+    [nb]) by a stable counting sort on the device, and the group offsets."""
+    L = lib()
+    assert blk_i.dim() == 1 and blk_i.dtype == torch.int32 and blk_i.is_contiguous() and blk_i.is_cuda
+    nb = blk_i.shape[0]
+    wsb = int(L.ttr_sparse_group_workspace_bytes(nb, int(I)))
+    if wsb < 0:
+        _check(wsb, "ttr_sparse_group_workspace_bytes")
+    ilist = torch.empty(nb, dtype=torch.int32, device=blk_i.device)
+    iptr = torch.empty(I + 1, dtype=torch.int32, device=blk_i.device)
+    ws = _workspace(wsb, blk_i.device, 16)
+    _call("ttr_sparse_group", nb, int(I), blk_i.data_ptr(), ilist.data_ptr(), iptr.data_ptr(), ws.data_ptr(), wsb)
+    return ilist, iptr
+
+
+def sparse_gram_parts(dt: torch.dtype, r: int, I: int, nb: int) -> int:
+    p = int(lib().ttr_sparse_gram_parts(dtype_code(dt), int(r), int(I), int(nb)))
+    if p < 0:
+        _check(p, "ttr_sparse_gram_parts")
+    return p
+
+
+@_on_device
+def sparse_gram(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.Tensor, blkcol: torch.Tensor, ilist: torch.Tensor,
+                iptr: torch.Tensor) -> torch.Tensor:
+    """ttr_sparse_gram: G [r I, r I] = D D^T of the block table (V [nb, r]; integer device arrays colptr [C + 1], blk_i [nb],
+    blkcol [nb], ilist [nb], iptr [I + 1], passed on as int32) -- see include/ttround_hip.h."""
+    L = lib()
+    colptr, blk_i, blkcol, ilist, iptr = (a.to(torch.int32) for a in (colptr, blk_i, blkcol, ilist, iptr))
+    dt = dtype_code(V.dtype)
+    assert V.dim() == 2 and (V.shape[1] == 1 or V.stride(1) == 1)
+    nb, r = V.shape
+    C = colptr.shape[0] - 1
+    for a, n in ((colptr, C + 1), (blk_i, nb), (blkcol, nb), (ilist, nb), (iptr, I + 1)):
+        assert a.is_contiguous() and a.shape[0] == n and a.device == V.device
+    wsb = int(L.ttr_sparse_gram_workspace_bytes(dt, r, I, nb))
+    if wsb < 0:
+        _check(wsb, "ttr_sparse_gram_workspace_bytes")
+    n = r * I
+    G = torch.empty((n, n), dtype=V.dtype, device=V.device)
+    ws = _workspace(wsb, V.device, 16)
+    _call("ttr_sparse_gram", dt, r, I, nb, C, colptr.data_ptr(), blk_i.data_ptr(), blkcol.data_ptr(), ilist.data_ptr(),
+          iptr.data_ptr(), V.data_ptr(), int(V.stride(0)) if nb > 1 else r, G.data_ptr(), n, ws.data_ptr(), wsb)
+    return G
+
+
+@_on_device
+def sparse_project(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.Tensor, U: torch.Tensor, q: int) -> torch.Tensor:
+    """ttr_sparse_project: W [C, q], W[c] = sum over the blocks b of column c of V[b] @ core[:, blk_i[b], :], core = U[:, :q]
+    viewed as [r, I, q] (U [r I, >= q], any strides: read where it lies)."""
+    dt = dtype_code(V.dtype)
+    assert V.dim() == 2 and (V.shape[1] == 1 or V.stride(1) == 1) and U.dim() == 2 and U.dtype == V.dtype
+    nb, r = V.shape
+    C = colptr.shape[0] - 1
+    assert U.shape[0] == r * I and U.shape[1] >= q
+    colptr, blk_i = colptr.to(torch.int32), blk_i.to(torch.int32)
+    assert colptr.is_contiguous() and blk_i.is_contiguous() and blk_i.shape[0] == nb
+    W = torch.empty((C, q), dtype=V.dtype, device=V.device)
+    _call("ttr_sparse_project", dt, r, I, q, nb, C, colptr.data_ptr(), blk_i.data_ptr(), V.data_ptr(),
+          int(V.stride(0)) if nb > 1 else r, U.data_ptr(), int(U.stride(0)), int(U.stride(1)), W.data_ptr(), q)
+    return W

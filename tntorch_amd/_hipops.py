@@ -312,25 +312,28 @@ def _bj_finish(G0, G, V, relative):
     return V, d
 
 
-def _eigh_any(G: torch.Tensor, eig_mode: int, use_delta: bool, delta2: float, cap: int, solver: int, prerotation: bool = False):
+def _eigh_any(G: torch.Tensor, eig_mode: int, use_delta: bool, delta2: float, cap: int, solver: int, prerotation: bool = False,
+              delta2_dev: Optional[torch.Tensor] = None):
     """Dispatch on the problem size: n <= LDS limit -> one workgroup per matrix (tridiagonal QL for n <= 64 when
     requested, Jacobi otherwise); larger -> block Jacobi over the GPU, then one (rotation-free) pass of the
     Jacobi kernel for its epilogue (clamp, sqrt, sort, rank rule).  Sizes no block width in 8..32 divides are
-    padded with decoupled rows/columns whose eigenvalue -||G||_F lies below every real one."""
+    padded with decoupled rows/columns whose eigenvalue -||G||_F lies below every real one.
+    ``delta2_dev`` (device double [1], optional): the rank rule's delta^2 read from device memory instead of ``delta2``."""
     Bt, n, _ = G.shape
     lds_limit = _hip.lib().ttr_eigh_max_n_lds(_hip.dtype_code(G.dtype))
     if n <= lds_limit:
-        return _hip.eigh_trunc(G, eig_mode, use_delta, delta2, cap, abs_floor=solver)
+        return _hip.eigh_trunc(G, eig_mode, use_delta, delta2, cap, abs_floor=solver, delta2_dev=delta2_dev)
     relative = solver != _hip.SOLVER_TRIDIAG
     if _bj_block(n) is not None:
         Vb, d = eigh_block_jacobi(G, relative=relative, prerotation=prerotation)
-        P, sig, info = _hip.eigh_trunc(torch.diag_embed(d), eig_mode, use_delta, delta2, cap, abs_floor=_hip.SOLVER_JACOBI_ABS)
+        P, sig, info = _hip.eigh_trunc(torch.diag_embed(d), eig_mode, use_delta, delta2, cap, abs_floor=_hip.SOLVER_JACOBI_ABS,
+                                       delta2_dev=delta2_dev)
         return _hip.gemm(Vb, P), sig, info
     nblk = -(-n // 32)
     b = -(-n // nblk)
     npad = nblk * b
     if npad > _hip.max_eigh_n(G.dtype):
-        return _hip.eigh_trunc(G, eig_mode, use_delta, delta2, cap, abs_floor=solver)
+        return _hip.eigh_trunc(G, eig_mode, use_delta, delta2, cap, abs_floor=solver, delta2_dev=delta2_dev)
     gn = _hip.norm(G.reshape(Bt, -1))                                     # >= |lambda|_max
     Gp = G.new_zeros((Bt, npad, npad))
     Gp[:, :n, :n] = G
@@ -345,7 +348,7 @@ def _eigh_any(G: torch.Tensor, eig_mode: int, use_delta: bool, delta2: float, ca
     Vs = _hip.gemm(Vb, P1)[:, :n, :n].contiguous()                        # real eigenvectors, decreasing eigenvalue
     ds = torch.diagonal(_hip.gemm(P1, _hip.gemm(torch.diag_embed(d), P1), transA=True), dim1=1, dim2=2)[:, :n]
     P2, sig, info = _hip.eigh_trunc(torch.diag_embed(ds.contiguous()), eig_mode, use_delta, delta2, cap,
-                                    abs_floor=_hip.SOLVER_JACOBI_ABS)
+                                    abs_floor=_hip.SOLVER_JACOBI_ABS, delta2_dev=delta2_dev)
     return _hip.gemm(Vs, P2), sig, info
 
 
@@ -1928,3 +1931,51 @@ def als_core(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: tor
         _hip.spd_solve(Gp, hp, plan.toff[i0 : i1 + 1], t0, X, r1, Gsum, hsum, status, plan.counts[i0:i1])
         _pinv_fallback(Gsum, hsum, status, X, r1)
     return core
+
+
+# ------------------------------------------------------------------------------------------------ sparse TT-SVD (interpolation.py)
+def sparse_canonical(X: torch.Tensor, shape: Sequence[int]):
+    """The canonical sample order of ``sparse_tt_svd`` on the device: (perm, lev) as ``_hostops.sparse_canonical``.  Indices are
+    validated by ttr_sparse_keys, repeated positions found by ttr_sparse_levels, both into one flag word that is read once.  One
+    int64 key and one device sort when prod(shape) < 2^63, stable per-mode sorts otherwise."""
+    P, N = X.shape
+    shape_dev = torch.tensor([int(s) for s in shape], dtype=torch.int64).to(X.device)
+    flag = torch.empty(1, dtype=torch.int32, device=X.device)
+    if P >= 2**31:
+        raise NotImplementedError("sparse_tt_svd: {} samples, the device path takes fewer than 2^31".format(P))
+    size = math.prod(int(s) for s in shape)
+    if size < 2**63:
+        key = _hip.sparse_keys(X, shape_dev, flag)
+        if size < 2**31:
+            key = key.to(torch.int32)  # narrow keys: half the sort's scratch
+        perm = torch.sort(key).indices.to(torch.int32)
+        del key
+    else:
+        _hip.sparse_keys(X, shape_dev, flag, want_keys=False)
+        perm = torch.arange(P, device=X.device)
+        for n in range(N):
+            perm = perm[torch.sort(X[perm, n], stable=True).indices]
+        perm = perm.to(torch.int32)
+    lev = _hip.sparse_levels(X, perm, flag)
+    bits = int(flag.item())  # the one host read of the validation
+    if bits & 1:
+        raise ValueError("sparse_tt_svd: an index in X is negative or outside its mode")
+    if bits & 2:
+        raise ValueError("sparse_tt_svd: repeated positions in X")
+    return perm, lev
+
+
+def sparse_step(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.Tensor, blkcol: torch.Tensor,
+                delta2_dev: torch.Tensor, cap: int):
+    """One step of interpolation.py:135-181 on a block table without its dense D: ttr_sparse_gram, the eigensolver with the rank
+    rule on the device (delta^2 from device memory), one readback of the selected rank, ttr_sparse_project with the core read from
+    the eigenvector matrix.  Returns (left [r I, q], W [C, q]).  The eigensolver's zero guard (sigma_max < 1e-13 in absolute
+    terms, round.py:137-145) reports rank 0, taken as rank 1 here: samples that small come out at rank 1 whatever eps is."""
+    order, iptr = _hip.sparse_group(blk_i, I)                        # the blocks grouped by mode index, in block order
+    G = _hip.sparse_gram(V, I, colptr, blk_i, blkcol, order, iptr)
+    del order, iptr
+    U, _, info = _eigh_any(G[None], _hip.EIG_RAW, True, 0.0, cap, _hip.SOLVER_JACOBI_ABS, delta2_dev=delta2_dev)
+    del G
+    q = max(1, min(cap, int(info[0].item())))                         # (readback: sizes the next core)
+    W = _hip.sparse_project(V, I, colptr, blk_i, U[0], q)
+    return U[0][:, :q], W

@@ -476,3 +476,46 @@ def als_left_step(L: torch.Tensor, core: torch.Tensor, x: torch.Tensor) -> torch
 def als_right_step(R: torch.Tensor, core: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """rights[mu - 1] = core[:, X[:, mu], :] @ rights[mu] (interpolation.py:67-70, 88-91) on [P, r] interfaces."""
     return torch.einsum("apb,pb->pa", core[:, x, :], R)
+
+
+def sparse_canonical(X: torch.Tensor, shape: Sequence[int]):
+    """The canonical sample order of ``sparse_tt_svd`` on the CPU: (perm, lev) with perm the lexicographic order (x_N major, x_1
+    minor) and lev[p] the deepest mode, 1-based, in which sorted sample p differs from its predecessor (N for p = 0).  Raises
+    ValueError for indices outside ``shape`` and for repeated positions."""
+    P, N = X.shape
+    if int(X.min()) < 0:
+        raise ValueError("sparse_tt_svd: negative indices in X")
+    for n in range(N):
+        if int(X[:, n].max()) >= shape[n]:
+            raise ValueError("sparse_tt_svd: index {} out of range for mode {} of size {}".format(int(X[:, n].max()), n, shape[n]))
+    perm = torch.arange(P)
+    for n in range(N):  # stable sorts, minor key first
+        perm = perm[torch.sort(X[perm, n], stable=True).indices]
+    Xs = X[perm]
+    diff = Xs[1:] != Xs[:-1]
+    lev = torch.full((P,), N, dtype=torch.int32)
+    lev[1:] = (diff * torch.arange(1, N + 1)).max(dim=1).values.to(torch.int32)
+    if P > 1 and int(lev[1:].min()) == 0:
+        raise ValueError("sparse_tt_svd: repeated positions in X")
+    return perm.to(torch.int32), lev
+
+
+def sparse_step(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.Tensor, blkcol: torch.Tensor, delta: float,
+                cap: int):
+    """One step of interpolation.py:135-181 on a block table (V [nb, r]; column c owns the blocks colptr[c]:colptr[c+1], block b
+    sits at mode index blk_i[b]): the dense D [r I, C] of ``sparse_covariance``, ``D D^T``, ``torch.linalg.eigh``, the
+    reference's rank rule capped at ``cap``, and ``left^T D``.  Returns (left [r I, q], W [C, q] = (left^T D)^T)."""
+    nb, r = V.shape
+    C = colptr.shape[0] - 1
+    D = torch.zeros(r * I, C, dtype=V.dtype)
+    rows = torch.arange(r)[None, :] * I + blk_i.long()[:, None]
+    D[rows, blkcol.long()[:, None].expand(nb, r)] = V
+    w, v = torch.linalg.eigh(_mm(D, D.t()))
+    w = torch.sqrt(torch.clamp(w, min=0)).flip(0)  # decreasing importance
+    v = v.flip(1)
+    tail = torch.cumsum((w**2).flip(0), dim=0)
+    where = torch.where(tail <= delta**2)[0]
+    kept = len(w) if len(where) == 0 else len(w) - 1 - int(where[-1])
+    rank = max(1, min(cap, kept))
+    left = v[:, :rank]
+    return left, _mm(left.t(), D).t().contiguous()

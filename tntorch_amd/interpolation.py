@@ -1,5 +1,7 @@
-"""TT completion from samples (interpolation.py:9-119): ``als_completion`` builds a tensor train from P samples ``y`` at the
-integer positions ``X`` by alternating least squares.
+"""Tensor trains from samples (interpolation.py:9-218): ``als_completion`` builds a tensor train from P samples ``y`` at the
+integer positions ``X`` by alternating least squares, ``sparse_tt_svd`` (below) by a TT-SVD of the sparse tensor that holds them.
+
+``als_completion``
 
 Same signature, defaults, contract and printout as the reference, with three deliberate differences:
 
@@ -17,7 +19,23 @@ CPU trains run the reference's operator sequence (per-slice lstsq, einsum interf
 once by a stable argsort.  Device trains run, per core step, ``ttr_als_normal`` (the per-slice normal equations on the matrix
 cores), ``ttr_spd_solve`` (batched Cholesky; flagged slices go through ``ttr_eigh_trunc`` + ``ttr_gemm`` + ``ttr_pinv_finish``),
 the HIP orthogonalisation and one ``ttr_gather_step`` for the interface update; nothing is read back within the sweeps except,
-with ``verbose``, one value per sweep.  Batched ``x0``, ``sparse_tt_svd``, ``PCEInterpolator`` and autograd are out of scope.
+with ``verbose``, one value per sweep.  Batched ``x0``, ``PCEInterpolator`` and autograd are out of scope.
+
+``sparse_tt_svd`` (interpolation.py:122-218) is the TT-SVD of the tensor that holds the samples and zeros elsewhere; its relative
+error is at most ``eps``.  Same signature and defaults as the reference, with four deliberate differences:
+
+1. The cores live on ``y``'s device and in ``y``'s dtype (the reference casts through the default dtype).
+2. The rank of a bond is also capped by the number of columns (distinct index suffixes) of its unfolding.  The reference keeps up
+   to ``nrows`` directions; the extra ones are null vectors of the Gram matrix.
+3. Negative indices, and indices ``>= shape[n]`` when ``shape`` is given, raise ``ValueError``.
+4. Repeated positions raise ``ValueError`` (the reference lets the last write win, which has no defined order on a GPU).
+
+The samples are sorted once (x_N the major key, x_1 the minor one); in that order the columns of every step are contiguous runs
+whose entries ascend in the step's mode index.  CPU trains then run the reference's operator sequence per step (the dense matrix
+D of the unfolding, ``D D^T``, ``torch.linalg.eigh``, its rank rule, ``left^T D``).  Device trains never build D: per step
+``ttr_sparse_gram`` (work proportional to sum_c m_c^2 r^2 over the columns' entry counts m_c), the HIP eigensolver with the rank
+rule on the device, one readback of the selected rank, and ``ttr_sparse_project``.  ``PCEInterpolator``, batched output and
+autograd are out of scope.
 """
 
 from __future__ import annotations
@@ -26,8 +44,9 @@ import time
 
 import torch
 
-__all__ = ["als_completion"]
+__all__ = ["als_completion", "sparse_tt_svd"]
 
+_STEP_HOOK = None  # diagnostics: called with n after step n of sparse_tt_svd (memory / time per step)
 MAX_DEVICE_K = 1024  # r0 * r1 of a core: ttr_als_normal / ttr_spd_solve's limit
 
 
@@ -166,3 +185,103 @@ def als_completion(X, y, ranks_tt, shape=None, ws=None, x0=None, niter=10, verbo
             print(" | time: {:8.4f}".format(time.time() - start))
 
     return x0
+
+
+def sparse_tt_svd(X, y, eps, shape=None, rmax=None):
+    """TT-SVD for sparse tensors (interpolation.py:122-218): the tensor train of the tensor that holds ``y`` at the positions
+    ``X`` and zeros elsewhere.
+
+    Unlike the reference, the cores live on ``y``'s device and in ``y``'s dtype, the rank of a bond is also capped by the number
+    of columns of its unfolding, and bad indices (negative, or ``>= shape[n]`` for a given ``shape``) and repeated positions
+    raise ``ValueError`` (see the module docstring).  A mode index without a sample is a zero slice.  On a device every step's
+    unfolding needs ``rank * shape[n] <= 4096`` (fp32) / 2048 (fp64) rows; beyond that ``NotImplementedError`` names the bond.
+    With a finite ``rmax`` that check runs before any work on the WORST case ``min(rmax, rows, P) * shape[n]``, so a generous
+    ``rmax`` can refuse an input that ``rmax=None`` (checked step by step, on the ranks ``eps`` really selects) decomposes.  The
+    device eigensolver's zero guard treats ``sigma_max < 1e-13`` (absolute) as zero: samples that small give rank 1 whatever
+    ``eps`` is; scale ``y`` first.
+
+    :param X: matrix P X N of sample coordinates (integers; a torch tensor or a NumPy array)
+    :param y: P-sized vector of sample values (a torch tensor or a NumPy array)
+    :param eps: prescribed accuracy (resulting relative error is guaranteed to be not larger than this)
+    :param shape: input tensor shape. If not specified, a tensor will be chosen such that `X` fits in
+    :param rmax: optionally, cap all ranks above this value
+    :return: a TT (a :class:`Tensor`)
+    """
+    from .tensor import Tensor
+
+    X, y = torch.as_tensor(X), torch.as_tensor(y)
+    assert not X.dtype.is_floating_point
+    assert X.dim() == 2
+    assert y.dim() == 1 and y.dtype.is_floating_point
+    P, N = X.shape
+    if N < 2:
+        raise ValueError("sparse_tt_svd needs at least two modes")
+    if P == 0:
+        raise ValueError("sparse_tt_svd needs at least one sample")
+    assert y.shape[0] == P
+    device, dtype = y.device, y.dtype
+    on_dev = device.type != "cpu"
+    X = X.to(device).long()
+    if shape is None:
+        shape = (torch.max(X, dim=0)[0] + 1).tolist()
+        if min(shape) < 1:
+            raise ValueError("sparse_tt_svd: negative indices in X")
+    shape = [int(s) for s in shape]
+    assert N == len(shape)
+    if min(shape) < 1:
+        raise ValueError("sparse_tt_svd: empty mode in shape {}".format(shape))
+    if rmax is None:
+        rmax = 2**31 - 1
+    rmax = max(1, int(rmax))
+
+    if on_dev:
+        from . import _hip
+        from . import _hipops as ops
+
+        limit = _hip.max_eigh_n(dtype)
+        if rmax < 2**31 - 1:  # the bound is known in advance: before any work
+            bound = 1
+            for n in range(N - 1):
+                if bound * shape[n] > limit:
+                    raise NotImplementedError(_ENVELOPE.format(n + 1, bound, shape[n], bound * shape[n], limit, dtype))
+                bound = min(rmax, bound * shape[n], P)
+        # delta^2 = (eps / sqrt(N - 1) ||y||)^2 stays on the device (the rank rule reads it there)
+        delta = (_hip.norm(y.contiguous()[None]).double() ** 2) * (float(eps) ** 2 / (N - 1))
+    else:
+        from . import _hostops as ops
+
+        delta = float(eps) / (N - 1) ** 0.5 * float(torch.norm(y))
+
+    perm, lev = ops.sparse_canonical(X, shape)
+    V = y[perm][:, None].contiguous()  # [blocks, r]: the blocks of step 1 are the sorted samples, r = 1
+    first = None  # sorted position of the first sample of every block (None: every sample is a block)
+    cores = []
+    for n in range(1, N):
+        I, r, nb = shape[n - 1], V.shape[1], V.shape[0]
+        if on_dev and r * I > limit:
+            raise NotImplementedError(_ENVELOPE.format(n, r, I, r * I, limit, dtype))
+        mark = lev >= n + 1  # a new column of this step (a new suffix x_{n+1..N}) starts at these sorted samples
+        start = torch.nonzero(mark)[:, 0].to(torch.int32)
+        C = int(start.shape[0])
+        i32 = torch.int32  # the block table travels as int32 (P < 2^31)
+        xn = X[:, n - 1].to(i32)
+        if first is None:
+            blk_i, blkcol, ptr = xn[perm], torch.cumsum(mark, dim=0, dtype=i32) - 1, start
+        else:
+            blk_i, blkcol = xn[perm[first]], torch.cumsum(mark[first], dim=0, dtype=i32) - 1
+            ptr = torch.searchsorted(first, start, out_int32=True)
+        del xn
+        colptr = torch.cat([ptr, torch.full((1,), nb, dtype=i32, device=device)])
+        del mark
+        left, V = ops.sparse_step(V, I, colptr, blk_i.contiguous(), blkcol, delta, min(rmax, r * I, C))
+        cores.append(left.reshape(r, I, left.shape[1]).contiguous())
+        first = start
+        if _STEP_HOOK is not None:
+            _STEP_HOOK(n)
+    last = torch.zeros(V.shape[1], shape[-1], 1, dtype=dtype, device=device)
+    last[:, X[:, N - 1][perm[first]], 0] = V.t()
+    cores.append(last)
+    return Tensor(cores)
+
+
+_ENVELOPE = ("sparse_tt_svd: the unfolding of bond {} has rank {} x size {} = {} rows, above the device limit of {} for {}")
