@@ -55,7 +55,7 @@ extern "C" {
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
-#define TTR_ABI_VERSION 15
+#define TTR_ABI_VERSION 16
 int ttr_version(void);
 const char* ttr_last_error(void);
 
@@ -823,6 +823,38 @@ int ttr_sparse_gram(int dtype, int64_t r, int64_t I, int64_t nb, int64_t C, cons
 int ttr_sparse_project(int dtype, int64_t r, int64_t I, int64_t q, int64_t nb, int64_t C, const void* colptr, const void* blk_i,
                        const void* V, int64_t ldv, const void* U, int64_t su_row, int64_t su_col, void* W, int64_t ldw,
                        void* stream);
+
+/*
+ * Contractions of the TT moment family (ABI 16; metrics.py:345-455, `hadamard_sum`), both on v_mfma_f32_16x16x4_f32 /
+ * v_mfma_f64_16x16x4_f64 (true fp32 / fp64 inputs), both without host synchronisation.
+ *
+ * ttr_core_matvec   the product of a TT-matrix core with a TT-vector core (metrics.py:434-445, `einsum("ijkl,akbc->iajblc")`
+ *                   with j = 1 and the reshape that follows it):
+ *                       out[p A + a, s, q C + c] = sum_k x[p, k, q] G[a, k, s, c]
+ *                   x [P, K, Q], G [A, K, S, C], out [P A, S, Q C], all contiguous.  The element strides of x (3) and G (4) are
+ *                   passed as HOST arrays and checked: anything but the strides of a contiguous tensor (the stride of an
+ *                   extent-1 axis is free) is refused with TTR_E_UNSUPPORTED before a byte is read.  The result is written in
+ *                   its Kronecker-interleaved layout directly: neither operand is permuted or copied and there is no
+ *                   un-permuted intermediate.  A C and P S at most 2^31 - 1.
+ * ttr_hsum_step     one mode of the exact K-way chain (metrics.py:407-425):
+ *                       W'[a'_1 .. a'_K] = sum_i sum_{a_1 .. a_K} W[a_1 .. a_K] prod_m A_m[a_m, i, a'_m]
+ *                   W [r_in[0], .., r_in[K-1]] and W' [r_out[0], .., r_out[K-1]] contiguous, `cores` a HOST array of K device
+ *                   pointers A_m [r_in[m], I, r_out[m]], `core_strides` a HOST array of their 3 K element strides, checked as
+ *                   above (TTR_E_UNSUPPORTED).  Modes 1 .. K-1 are batched products on strided views -- the mode index i is a
+ *                   batch index of the core and a stride-0 index of W: nothing is repeated or permuted -- and the last mode
+ *                   contracts (i, a_K) at once, length I r_in[K-1], which sums over i.  1 <= K <= 8.
+ *                   Scratch: the intermediates T_m [I, r_out[0 .. m], r_in[m+1 .. K-1]], m = 0 .. K-2, alternate between two
+ *                   halves of `workspace`; ttr_hsum_step_workspace_bytes =
+ *                       2 * align256( sizeof(dtype) * I * max_m prod_{j <= m} r_out[j] prod_{j > m} r_in[j] )     (0 for K = 1)
+ *                   and at most 2^32 bytes: beyond that, or with prod(r_in) / prod(r_out) / I r above 2^31 - 1, the query
+ *                   returns TTR_E_UNSUPPORTED (< 0) and so does the entry.  A smaller `workspace_bytes` is TTR_E_WORKSPACE.
+ */
+int ttr_core_matvec(int dtype, int64_t P, int64_t K, int64_t Q, int64_t A, int64_t S, int64_t C, const void* x,
+                    const int64_t* x_strides, const void* G, const int64_t* g_strides, void* out, void* stream);
+int64_t ttr_hsum_step_workspace_bytes(int dtype, int64_t K, int64_t I, const int64_t* r_in, const int64_t* r_out);
+int ttr_hsum_step(int dtype, int64_t K, int64_t I, const int64_t* r_in, const int64_t* r_out, const void* W,
+                  const void* const* cores, const int64_t* core_strides, void* Wout, void* workspace, int64_t workspace_bytes,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -1202,3 +1202,47 @@ def sparse_project(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.T
     _call("ttr_sparse_project", dt, r, I, q, nb, C, colptr.data_ptr(), blk_i.data_ptr(), V.data_ptr(),
           int(V.stride(0)) if nb > 1 else r, U.data_ptr(), int(U.stride(0)), int(U.stride(1)), W.data_ptr(), q)
     return W
+
+
+def _i64(values):
+    return (c_int64 * len(values))(*[int(v) for v in values])
+
+
+@_on_device
+def core_matvec(x: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """ttr_core_matvec: x [P, K, Q], G [A, K, S, C] -> out [P A, S, Q C], out[p A + a, s, q C + c] = sum_k x[p, k, q] G[a, k, s, c].
+    The operands are passed with the strides they have: the library refuses anything but contiguous ones."""
+    dt = dtype_code(x.dtype)
+    assert x.dim() == 3 and G.dim() == 4 and x.dtype == G.dtype and x.shape[1] == G.shape[1] and G.device == x.device
+    P, K, Q = x.shape
+    A, _, S, C = G.shape
+    out = torch.empty((P * A, S, Q * C), dtype=x.dtype, device=x.device)
+    _call("ttr_core_matvec", dt, P, K, Q, A, S, C, x.data_ptr(), _i64(x.stride()), G.data_ptr(), _i64(G.stride()), out.data_ptr())
+    return out
+
+
+def hsum_step_workspace_bytes(dt: torch.dtype, I: int, r_in, r_out) -> int:
+    """ttr_hsum_step_workspace_bytes; a negative status (TTR_E_UNSUPPORTED: the ranks leave the entry's envelope) is returned."""
+    return int(lib().ttr_hsum_step_workspace_bytes(dtype_code(dt), len(r_in), int(I), _i64(r_in), _i64(r_out)))
+
+
+@_on_device
+def hsum_step(W: torch.Tensor, cores, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_hsum_step: W [r_1, .., r_K] (contiguous), cores A_m [r_m, I, r'_m] -> W' [r'_1, .., r'_K],
+    W'[a'] = sum_i sum_a W[a] prod_m A_m[a_m, i, a'_m].  ``workspace``: a uint8 device tensor of at least
+    hsum_step_workspace_bytes(...) bytes (allocated here when None)."""
+    dt = dtype_code(W.dtype)
+    K = len(cores)
+    assert K >= 1 and W.dim() == K and W.is_contiguous() and all(c.dim() == 3 and c.dtype == W.dtype and c.device == W.device for c in cores)
+    I = cores[0].shape[1]
+    r_in, r_out = [c.shape[0] for c in cores], [c.shape[2] for c in cores]
+    assert list(W.shape) == r_in and all(c.shape[1] == I for c in cores)
+    wsb = hsum_step_workspace_bytes(W.dtype, I, r_in, r_out)
+    if wsb < 0:
+        _check(wsb, "ttr_hsum_step_workspace_bytes")
+    ws = workspace if workspace is not None else _workspace(wsb, W.device)
+    out = torch.empty(r_out, dtype=W.dtype, device=W.device)
+    ptrs = (c_void_p * K)(*[c.data_ptr() for c in cores])
+    _call("ttr_hsum_step", dt, K, I, _i64(r_in), _i64(r_out), W.data_ptr(), ptrs, _i64([s for c in cores for s in c.stride()]),
+          out.data_ptr(), _ptr(ws), int(ws.numel()) if ws is not None else 0)
+    return out

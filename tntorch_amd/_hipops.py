@@ -41,7 +41,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _hip
+from . import _hip, _hostops
 
 INT32_MAX = 2**31 - 1
 # set by the API layer around a call with verbose=True: the reference's per-stage timing lines (round.py:95-117, 163-185;
@@ -1665,6 +1665,31 @@ def dense_dist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     one = torch.ones((1, 1, 1), dtype=a.dtype, device=a.device)
     _hip.gemm_axpby(b.reshape(1, n, 1), one, d, -1.0, 1.0)
     return _hip.norm(d.reshape(1, -1))[0]
+
+
+# ---------------------------------------------------------------------------------------------- moments (metrics.py:345-455)
+def core_matvec(x: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """metrics.py:434-445 (ttr_core_matvec): G [A, K, S, C] times x [P, K, Q] -> [P A, S, Q C], written interleaved."""
+    return _hip.core_matvec(x.contiguous(), G.contiguous())
+
+
+def hsum_step(W: torch.Tensor, cores: Sequence[torch.Tensor]) -> torch.Tensor:
+    """metrics.py:407-425, one mode (ttr_hsum_step): W [r_1, .., r_K], cores A_m [r_m, I, r'_m] -> W' [r'_1, .., r'_K].
+    ValueError when the intermediates of these ranks need more scratch than the entry accepts."""
+    wsb = _hip.hsum_step_workspace_bytes(W.dtype, cores[0].shape[1], [c.shape[0] for c in cores], [c.shape[2] for c in cores])
+    if wsb == _hip.E_UNSUPPORTED:
+        raise ValueError(
+            "hadamard_sum: the exact algorithm on ranks {} x {} needs more scratch than ttr_hsum_step accepts "
+            '(prod of the ranks times the mode size); use algorithm="eig"'.format([c.shape[0] for c in cores], [c.shape[2] for c in cores]))
+    return _hip.hsum_step(W.contiguous(), [c.contiguous() for c in cores])
+
+
+# the diagonal cores are a scatter of I Rl Rr values into zeros: torch's indexing on the device (DESIGN section 15)
+diag_cores = _hostops.diag_cores
+
+
+def sum_all(x: torch.Tensor) -> torch.Tensor:
+    return _sum_all(x.contiguous())
 
 
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1, C4)

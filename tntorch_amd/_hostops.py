@@ -293,6 +293,56 @@ def dense_dot(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return a.flatten().dot(b.flatten())
 
 
+# ---------------------------------------------------------------------------------------------- moments (metrics.py:345-455)
+def core_matvec(x: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """metrics.py:434-445: TT-matrix core G [A, K, S, C] times TT-vector core x [P, K, Q] -> [P A, S, Q C],
+    out[p A + a, s, q C + c] = sum_k x[p, k, q] G[a, k, s, c]."""
+    P, K, Q = x.shape
+    A, _, S, C = G.shape
+    return torch.einsum("pkq,aksc->pasqc", x, G).reshape(P * A, S, Q * C)
+
+
+def hsum_step(W: torch.Tensor, cores: Sequence[torch.Tensor]) -> torch.Tensor:
+    """metrics.py:407-425, one mode: W [r_1, .., r_K], cores A_m [r_m, I, r'_m] -> W' [r'_1, .., r'_K],
+    W'[a'] = sum_i sum_a W[a] prod_m A_m[a_m, i, a'_m]."""
+    K = len(cores)
+    I = cores[0].shape[1]
+    T = W[None].expand((I,) + tuple(W.shape))
+    for m, A in enumerate(cores):  # mode product m on the view [I, left, r_m, right]; the mode index i is a batch index
+        left = math.prod(T.shape[1:1 + m])
+        T3 = T.reshape(I, left, A.shape[0], -1)
+        T = torch.einsum("ilar,aib->ilbr", T3, A).reshape(tuple(T.shape[:1 + m]) + (A.shape[2],) + tuple(T.shape[2 + m:]))
+    return T.sum(dim=0)
+
+
+def diag_cores(cs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """metrics.py:358-382 (``diag_core`` / ``get_tensor`` before its rounding): the cores c_m [Rl_m, I, Rr_m] of ONE mode of M
+    trains -> the M cores [1, I or 1, Rl_m Rr_m, I or 1] of the train over the rank pairs whose bond is the mode index,
+    D_m[i, (a, b), j] = delta_ij c_m[a, i, b] (summed over i for m = 0 and over j for m = M - 1).  Index plumbing: I Rl Rr
+    values are scattered into zeros -- torch does it on whichever device the cores live."""
+    M = len(cs)
+    out = []
+    for m, c in enumerate(cs):
+        Rl, I, Rr = c.shape
+        F = c.permute(1, 0, 2).reshape(I, Rl * Rr)
+        if M == 1:
+            D = F.sum(dim=0).reshape(1, Rl * Rr, 1)
+        elif m == 0:
+            D = F.t()[None]
+        elif m == M - 1:
+            D = F[:, :, None]
+        else:
+            D = c.new_zeros((I, Rl * Rr, I))
+            idx = torch.arange(I, device=c.device)
+            D[idx, :, idx] = F
+        out.append(D.contiguous()[None])
+    return out
+
+
+def sum_all(x: torch.Tensor) -> torch.Tensor:
+    return x.sum()
+
+
 def dense_norm(a: torch.Tensor) -> torch.Tensor:
     return torch.norm(a)
 

@@ -580,3 +580,16 @@ class Tensor(object):
         reached = relative_error(copy, self)
         if reached < eps:
             self.round_tucker((1 + eps) / (1 + float(reached)) - 1, **kwargs)
+
+    # ------------------------------------------------------------------ convenience "methods" (tensor.py:2125-2137)
+    def var(self, **kwargs):
+        """See :func:`metrics.var`."""
+        from .metrics import var
+
+        return var(self, **kwargs)
+
+    def std(self, **kwargs):
+        """See :func:`metrics.std`."""
+        from .metrics import std
+
+        return std(self, **kwargs)
