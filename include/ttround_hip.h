@@ -53,9 +53,9 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
-#define TTR_ABI_VERSION 16
+#define TTR_ABI_VERSION 17
 int ttr_version(void);
 const char* ttr_last_error(void);
 
@@ -855,6 +855,38 @@ int64_t ttr_hsum_step_workspace_bytes(int dtype, int64_t K, int64_t I, const int
 int ttr_hsum_step(int dtype, int64_t K, int64_t I, const int64_t* r_in, const int64_t* r_out, const void* W,
                   const void* const* cores, const int64_t* core_strides, void* Wout, void* workspace, int64_t workspace_bytes,
                   void* stream);
+
+/*
+ * Differential operators on one TT core (ABI 17; derivatives.py:72-130 `partial`, 286-302 `laplacian`): streaming kernels, plain
+ * vector loads and stores (16 bytes per lane when C, the strides and the pointers are multiples of 16 bytes, else one element),
+ * no host synchronisation, no scratch.  The passes run in fp64 registers for both dtypes, without contraction, and the result is
+ * rounded once, at the store: where (inv_step S)^order annihilates the data (S^3 = 0 for I = 3) fp32 input gives exact zeros.
+ *
+ * S is the reference's I x I central-difference matrix (derivatives.py:96-129): interior rows e[i+1] - e[i-1], row 0 =
+ * 2 (e[1] - e[0]) and row I-1 = 2 (e[I-1] - e[I-2]) (its linearly extrapolated edge; I = 1 gives zeros), or, with `periodic`,
+ * roll(-1) - roll(+1).  `inv_step` = 1 / step, step = (b1 - b0) / (I + 1) * 2.
+ *
+ * ttr_mode_diff     Y = (inv_step S)^order X along the middle axis of X [R, I, C] (a Tucker factor [I, R'] is R = 1, C = R').
+ *                   X is contiguous: its 3 element strides are passed as a HOST array and checked as ttr_core_matvec checks
+ *                   them (TTR_E_UNSUPPORTED before a byte is read; the stride of an extent-1 axis is free).  Y has the element
+ *                   strides y_strides = (sr, si, 1) with si >= C and sr >= I si (else TTR_E_UNSUPPORTED): the result can be
+ *                   written straight into a block of a wider core, and nothing outside the block is touched.  X == Y,
+ *                   order < 1, I < 1 are TTR_E_INVALID.  The lanes walk the flattened (i, c) axis, so the neighbours at +- C are
+ *                   contiguous runs for every C.  1 <= order <= ttr_mode_diff_max_order() (= 4) passes run in ONE launch, X
+ *                   read from HBM once (2 order + 1 rows per thread in registers); a higher order is TTR_E_UNSUPPORTED: the
+ *                   caller chains calls ((inv_step S)^5 = (inv_step S)^1 (inv_step S)^4).
+ * ttr_laplace_core  one core of the exact rank-2r train of sum_n (inv_step_n S_n)^2, written whole in one
+ *                   launch from one read of X [R, I, C] (contiguous, checked as above), with D = (inv_step S)^2 X:
+ *                       pos 0 (first):   out [R, I, 2C]  = [X D]
+ *                       pos 1 (middle):  out [2R, I, 2C] = [[X, D], [0, X]]
+ *                       pos 2 (last):    out [2R, I, C]  = [D ; X]
+ *                   `out` is contiguous; both copies of X are bit-identical to it and the zero block is exactly zero.
+ */
+int ttr_mode_diff_max_order(void);
+int ttr_mode_diff(int dtype, int64_t R, int64_t I, int64_t C, int order, int periodic, double inv_step, const void* X,
+                  const int64_t* x_strides, void* Y, const int64_t* y_strides, void* stream);
+int ttr_laplace_core(int dtype, int64_t R, int64_t I, int64_t C, int pos, int periodic, double inv_step, const void* X,
+                     const int64_t* x_strides, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,9 @@ that sit on the TT decomposition / rounding hot path: ``tn.Tensor``, ``tn.round_
 ``tn.round``, ``tn.truncated_svd``, the unfoldings, plus the small helpers the reference's
 tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``), and TT-cross (``tn.cross``, ``tn.maxvol``,
 ``tn.meshgrid`` and the element-wise functions of ``ops``: ``tn.exp``, ``tn.cos``, ...), and TT completion from samples
-(``tn.als_completion``).
+(``tn.als_completion``), sparse TT-SVD (``tn.sparse_tt_svd``), the moment family (``tn.hadamard_sum``, ``tn.raw_moment``,
+``tn.normalized_moment``, ``tn.var``, ``tn.std``) and the differential operators of ``derivatives.py`` (``tn.partial``,
+``tn.gradient``, ``tn.divergence``, ``tn.curl``, ``tn.laplacian``, ``tn.dgsm``, ``tn.active_subspace``).
 """
 
 from .tools import *  # noqa: F401,F403
@@ -18,6 +20,7 @@ from .maxvol import *  # noqa: F401,F403
 from .cross import *  # noqa: F401,F403
 from .ops import *  # noqa: F401,F403
 from .interpolation import *  # noqa: F401,F403
+from .derivatives import *  # noqa: F401,F403
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

@@ -1246,3 +1246,45 @@ def hsum_step(W: torch.Tensor, cores, workspace: Optional[torch.Tensor] = None) 
     _call("ttr_hsum_step", dt, K, I, _i64(r_in), _i64(r_out), W.data_ptr(), ptrs, _i64([s for c in cores for s in c.stride()]),
           out.data_ptr(), _ptr(ws), int(ws.numel()) if ws is not None else 0)
     return out
+
+
+def mode_diff_max_order() -> int:
+    """ttr_mode_diff_max_order: the number of passes ttr_mode_diff fuses into one launch."""
+    return int(lib().ttr_mode_diff_max_order())
+
+
+@_on_device
+def mode_diff(X: torch.Tensor, order: int, periodic: bool, inv_step: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_mode_diff: Y = (inv_step S)^order X along the middle axis of X [R, I, C].  ``out``: a [R, I, C] view with element
+    strides (sr, si, 1) that receives the result (e.g. a block of a wider core); a fresh contiguous tensor when None.  X is passed
+    with the strides it has: the library refuses anything but contiguous ones.  Orders above the fused limit are chained here:
+    full launches into contiguous temporaries, the last one into ``out``."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and (out is None or (tuple(out.shape) == tuple(X.shape) and out.dtype == X.dtype and out.device == X.device))
+    R, I, C = X.shape
+    order = int(order)
+    Y = out if out is not None else torch.empty((R, I, C), dtype=X.dtype, device=X.device)
+    left = max(order, 1)
+    fused = mode_diff_max_order()
+    while True:
+        o = order if order < 1 else min(left, fused)   # (a bad order goes to the library as it is: TTR_E_INVALID)
+        left -= o
+        dst = Y if left <= 0 else torch.empty((R, I, C), dtype=X.dtype, device=X.device)
+        _call("ttr_mode_diff", dt, R, I, C, o, int(bool(periodic)), float(inv_step), X.data_ptr(), _i64(X.stride()), dst.data_ptr(),
+              _i64(dst.stride()))
+        if left <= 0:
+            return Y
+        X = dst
+
+
+@_on_device
+def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> torch.Tensor:
+    """ttr_laplace_core: X [R, I, C] -> [X D] (pos 0, [R, I, 2C]), [[X, D], [0, X]] (pos 1, [2R, I, 2C]) or [D ; X] (pos 2,
+    [2R, I, C]) with D = (inv_step S)^2 X, one launch."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3
+    R, I, C = X.shape
+    shape = {0: (R, I, 2 * C), 1: (2 * R, I, 2 * C), 2: (2 * R, I, C)}.get(int(pos), (2 * R, I, 2 * C))
+    out = torch.empty(shape, dtype=X.dtype, device=X.device)
+    _call("ttr_laplace_core", dt, R, I, C, int(pos), int(bool(periodic)), float(inv_step), X.data_ptr(), _i64(X.stride()), out.data_ptr())
+    return out

@@ -1692,6 +1692,18 @@ def sum_all(x: torch.Tensor) -> torch.Tensor:
     return _sum_all(x.contiguous())
 
 
+# ---------------------------------------------------------------------------------------------- derivatives (derivatives.py:72-302)
+def mode_diff(X: torch.Tensor, order: int, periodic: bool, inv_step: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """derivatives.py:96-129 (ttr_mode_diff): (inv_step S)^order along the middle axis of X [R, I, C]; ``out`` may be a block of a
+    wider core (element strides (sr, si, 1))."""
+    return _hip.mode_diff(X.contiguous(), order, periodic, inv_step, out)
+
+
+def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> torch.Tensor:
+    """One block core of the rank-2r Laplacian train (ttr_laplace_core): pos 0 [X D], 1 [[X, D], [0, X]], 2 [D ; X]."""
+    return _hip.laplace_core(X.contiguous(), pos, periodic, inv_step)
+
+
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1, C4)
 def _sum_all(x: torch.Tensor) -> torch.Tensor:
     """Sum of all entries as a 1 x n x 1 GEMM with a ones vector (split-K); returns a 0-d tensor."""

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import math
 import time
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -349,6 +349,53 @@ def dense_norm(a: torch.Tensor) -> torch.Tensor:
 
 def dense_dist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.dist(a, b)
+
+
+# ---------------------------------------------------------------------------------------------- derivatives (derivatives.py:72-302)
+def _diff_pass(X: torch.Tensor, periodic: bool, inv_step: float) -> torch.Tensor:
+    """One pass of derivatives.py:96-129 on X [R, I, C]: interior rows x[i+1] - x[i-1], rows 0 and I-1 twice the one-sided
+    difference (the reference's linearly extrapolated edge), or roll(-1) - roll(+1); times inv_step."""
+    I = X.shape[1]
+    if periodic:
+        return (torch.roll(X, -1, 1) - torch.roll(X, 1, 1)) * inv_step
+    Y = torch.zeros_like(X)
+    if I == 1:
+        return Y
+    Y[:, 1:-1] = X[:, 2:] - X[:, :-2]
+    Y[:, 0] = 2 * (X[:, 1] - X[:, 0])
+    Y[:, -1] = 2 * (X[:, -1] - X[:, -2])
+    return Y * inv_step
+
+
+def mode_diff(X: torch.Tensor, order: int, periodic: bool, inv_step: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mirror of ttr_mode_diff: ``order`` passes along the middle axis of X [R, I, C]; ``out`` (a [R, I, C] view) receives the result."""
+    if order < 1:
+        raise ValueError("mode_diff: order {} < 1".format(order))
+    Y = X.double()   # as the kernel: the passes run in fp64 for both dtypes, one rounding at the end
+    for _ in range(int(order)):
+        Y = _diff_pass(Y, periodic, inv_step)
+    Y = Y.to(X.dtype)
+    if out is None:
+        return Y
+    out.copy_(Y)
+    return out
+
+
+def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> torch.Tensor:
+    """Mirror of ttr_laplace_core: pos 0 [X D] ([R, I, 2C]), 1 [[X, D], [0, X]] ([2R, I, 2C]), 2 [D ; X] ([2R, I, C]),
+    D = (inv_step S)^2 X."""
+    R, I, C = X.shape
+    if pos == 2:
+        out = X.new_empty((2 * R, I, C))
+        mode_diff(X, 2, periodic, inv_step, out=out[:R])
+        out[R:] = X
+        return out
+    out = X.new_zeros(((2 if pos == 1 else 1) * R, I, 2 * C))
+    out[:R, :, :C] = X
+    mode_diff(X, 2, periodic, inv_step, out=out[:R, :, C:])
+    if pos == 1:
+        out[R:, :, C:] = X
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1)
