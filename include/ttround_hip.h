@@ -53,7 +53,8 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve was ADDED under 17: no existing signature changed, and a library without the
+   symbol fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -887,6 +888,25 @@ int ttr_mode_diff(int dtype, int64_t R, int64_t I, int64_t C, int order, int per
                   const int64_t* x_strides, void* Y, const int64_t* y_strides, void* stream);
 int ttr_laplace_core(int dtype, int64_t R, int64_t I, int64_t C, int pos, int periodic, double inv_step, const void* X,
                      const int64_t* x_strides, void* out, void* stream);
+
+/*
+ * Mode-wise convolution of two TT cores, slice-wise Kronecker in the ranks (added under ABI 17; tools.py:579-647 `convolve`, computed exactly
+ * instead of by three cross approximations in the Fourier domain):
+ *     out[r1 S1 + s1, k, r2 S2 + s2] = sum_i a[r1, i, r2] c[s1, k + lo - i, s2],   0 <= k < K
+ * (terms with k + lo - i outside [0, J) are absent).  `a` [R1, I, R2], `c` [S1, J, S2] and `out` [R1 S1, K, R2 S2] are contiguous;
+ * the rank layout is ttr_core_kron's.  (lo, K) is a window of the full result of I + J - 1 entries: 0 <= lo, lo + K <= I + J - 1;
+ * only the window is computed.  Before any launch, `out` untouched: TTR_E_INVALID for a bad dtype, a size < 1, a bad window, a
+ * null pointer or out == a / out == c; TTR_E_UNSUPPORTED only where an extent, a rank product or the number of workgroups does
+ * not fit 32 bits.  No mode size is refused: the sum runs over the shorter mode (min(I, J) terms whichever argument that is),
+ * staged in LDS in chunks of at most ttr_core_convolve_max_taps() (= 32) terms, the partial sums staying in registers across the
+ * chunks.  A workgroup owns one row (r1, s1), 64 columns and 16 V values of k, V = 4 (fp32) / 2 (fp64) elements of a 16-byte
+ * store when R2 S2 is a multiple of V and `out` is 16-byte aligned, else 1.  Accumulation in the input precision (FMA), terms in
+ * increasing order of the shorter mode's index; every output is written exactly once, no atomics: bit-identical from run to run.
+ * Profiling kind: TTR_PROF_MISC.
+ */
+int ttr_core_convolve_max_taps(void);
+int ttr_core_convolve(int dtype, int64_t R1, int64_t I, int64_t R2, int64_t S1, int64_t J, int64_t S2, int64_t lo, int64_t K,
+                      const void* a, const void* c, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@ tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``),
 ``tn.meshgrid`` and the element-wise functions of ``ops``: ``tn.exp``, ``tn.cos``, ...), and TT completion from samples
 (``tn.als_completion``), sparse TT-SVD (``tn.sparse_tt_svd``), the moment family (``tn.hadamard_sum``, ``tn.raw_moment``,
 ``tn.normalized_moment``, ``tn.var``, ``tn.std``) and the differential operators of ``derivatives.py`` (``tn.partial``,
-``tn.gradient``, ``tn.divergence``, ``tn.curl``, ``tn.laplacian``, ``tn.dgsm``, ``tn.active_subspace``).
+``tn.gradient``, ``tn.divergence``, ``tn.curl``, ``tn.laplacian``, ``tn.dgsm``, ``tn.active_subspace``) and the exact
+convolution of two trains (``tn.convolve``).
 """
 
 from .tools import *  # noqa: F401,F403

@@ -1288,3 +1288,27 @@ def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> 
     out = torch.empty(shape, dtype=X.dtype, device=X.device)
     _call("ttr_laplace_core", dt, R, I, C, int(pos), int(bool(periodic)), float(inv_step), X.data_ptr(), _i64(X.stride()), out.data_ptr())
     return out
+
+
+
+def core_convolve_max_taps() -> int:
+    """ttr_core_convolve_max_taps: the terms of the sum ttr_core_convolve stages in LDS at once (longer sums are chunked)."""
+    return int(lib().ttr_core_convolve_max_taps())
+
+
+@_on_device
+def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Tensor:
+    """ttr_core_convolve: a [R1, I, R2], c [S1, J, S2] (contiguous) -> [R1 S1, K, R2 S2] with
+    out[r1 S1 + s1, k, r2 S2 + s2] = sum_i a[r1, i, r2] c[s1, k + lo - i, s2]: the window (lo, K) of the full result of
+    I + J - 1 entries.  ValueError for anything but two contiguous 3-d device cores of one dtype, or a window the library refuses."""
+    if a.dim() != 3 or c.dim() != 3 or a.dtype != c.dtype or a.device != c.device or not a.is_cuda:
+        raise ValueError("core_convolve: expected two 3-d cores of one dtype on one device")
+    if not (a.is_contiguous() and c.is_contiguous()):
+        raise ValueError("core_convolve: the cores must be contiguous")
+    dt = dtype_code(a.dtype)
+    R1, I, R2 = a.shape
+    S1, J, S2 = c.shape
+    lo, K = int(lo), int(K)
+    out = torch.empty((R1 * S1, max(K, 0), R2 * S2), dtype=a.dtype, device=a.device)
+    _call("ttr_core_convolve", dt, R1, I, R2, S1, J, S2, lo, K, a.data_ptr(), c.data_ptr(), out.data_ptr())
+    return out

@@ -1704,6 +1704,13 @@ def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> 
     return _hip.laplace_core(X.contiguous(), pos, periodic, inv_step)
 
 
+# ---------------------------------------------------------------------------------------------- convolution (tools.py:579-647)
+def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Tensor:
+    """One core of the exact convolution train (ttr_core_convolve): a [R1, I, R2], c [S1, J, S2] -> [R1 S1, K, R2 S2], the window
+    (lo, K) of the mode-wise convolution, slice-wise Kronecker in the ranks."""
+    return _hip.core_convolve(a.contiguous(), c.contiguous(), lo, K)
+
+
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1, C4)
 def _sum_all(x: torch.Tensor) -> torch.Tensor:
     """Sum of all entries as a 1 x n x 1 GEMM with a ones vector (split-K); returns a 0-d tensor."""

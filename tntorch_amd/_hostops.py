@@ -398,6 +398,34 @@ def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> 
     return out
 
 
+# ---------------------------------------------------------------------------------------------- convolution (tools.py:579-647)
+def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Tensor:
+    """Mirror of ttr_core_convolve: a [R1, I, R2], c [S1, J, S2] -> [R1 S1, K, R2 S2],
+    out[r1 S1 + s1, k, r2 S2 + s2] = sum_i a[r1, i, r2] c[s1, k + lo - i, s2] for the window 0 <= lo, lo + K <= I + J - 1 of the
+    full result.  One shifted multiply-add per index of the SHORTER mode, in increasing order, accumulated in the input dtype."""
+    if a.dim() != 3 or c.dim() != 3 or a.dtype != c.dtype or a.device != c.device:
+        raise ValueError("core_convolve: expected two 3-d cores of one dtype on one device")
+    R1, I, R2 = a.shape
+    S1, J, S2 = c.shape
+    lo, K = int(lo), int(K)
+    if min(R1, I, R2, S1, J, S2, K) < 1 or lo < 0 or lo + K > I + J - 1:
+        raise ValueError("core_convolve: bad sizes or window (lo = {}, K = {}) for modes {} and {}".format(lo, K, I, J))
+    out = a.new_zeros((R1, S1, K, R2, S2))
+    swap = J < I   # the roles are symmetric: sum_j c[j] a[k + lo - j]
+    short, long_ = (c, a) if swap else (a, c)
+    Q = long_.shape[1]
+    for p in range(short.shape[1]):
+        k0, k1 = max(0, p - lo), min(K, Q + p - lo)   # the k with 0 <= k + lo - p < Q
+        if k1 <= k0:
+            continue
+        x, y = short[:, p, :], long_[:, k0 + lo - p:k1 + lo - p, :]
+        if swap:
+            out[:, :, k0:k1] += x[None, :, None, None, :] * y[:, None, :, :, None]
+        else:
+            out[:, :, k0:k1] += x[:, None, None, :, None] * y[None, :, :, None, :]
+    return out.reshape(R1 * S1, K, R2 * S2)
+
+
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1)
 def cp_als(X: torch.Tensor, R: int, max_iter: int, tol: float, verbose: bool = False, batch: bool = False, init=None):
     """tensor.py:210-400, the reference's operator sequence on the CPU.  ``init=None``: HOSVD initialisation

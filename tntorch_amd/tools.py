@@ -1,6 +1,6 @@
 """Unfoldings of TT cores / dense tensors -- the layout contract of the hot path -- and the rounding tree.
 
-Mirror of ``tntorch/tools.py:211-258`` (same names, arguments and results).  All three are
+Mirror of ``tntorch/tools.py:211-258`` (same names, arguments and results), and ``convolve`` (tools.py:579-647).  All three are
 pure ``reshape``/``permute`` views: a core ``[r0, I, r1]`` is row-major, so its left
 unfolding has row index ``r0*I + i`` and its right unfolding column index ``i*R1 + r1`` --
 exactly the addressing the HIP kernels use (no data movement on either side).
@@ -11,7 +11,7 @@ import time
 import numpy as np
 import torch
 
-__all__ = ["meshgrid", "unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode"]
+__all__ = ["meshgrid", "unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode", "convolve"]
 
 
 def meshgrid(*axes, batch=False):
@@ -153,3 +153,74 @@ def shift_mode(t, n, shift, eps=1e-3):
         cores[c2] = right.reshape(1, newR2, I1, R3)
     t.cores = t._denorm(cores)
     return t
+
+
+# the keyword arguments of tn.cross that the reference's convolve hands on: accepted and ignored (nothing is cross-approximated)
+_CROSS_KWARGS = frozenset(["ranks_tt", "kickrank", "max_iter", "val_size", "verbose", "return_info", "record_samples", "device",
+                           "suppress_warnings", "detach_evaluations", "function_arg"])
+
+
+def convolve_window(I, J, mode):
+    """(lo, K): the entries lo .. lo + K - 1 of the full convolution (I + J - 1 entries) of modes of sizes I and J that
+    ``np.convolve`` returns for ``mode``."""
+    k, m = min(I, J), max(I, J)
+    if mode == "full":
+        return 0, I + J - 1
+    if mode == "same":
+        return (k - 1) // 2, m
+    if mode == "valid":
+        return k - 1, m - k + 1
+    raise ValueError("convolve: mode must be 'full', 'same' or 'valid', got {!r}".format(mode))
+
+
+def convolve(t1, t2, mode="full", eps=1e-6, rmax=None, algorithm="svd", **kwargs):
+    """N-D convolution of two tensors (tools.py:579-647), computed exactly: the convolution of two trains is a train whose core
+    ``n`` is the mode-wise convolution of the two cores, slice-wise Kronecker in the ranks,
+
+        C_n[r1 S1 + s1, k, r2 S2 + s2] = sum_i A_n[r1, i, r2] B_n[s1, k + lo - i, s2]
+
+    (one ``ttr_core_convolve`` launch per mode on device tensors; only the window of ``mode`` is computed).  Its ranks are the
+    products ``r s``; one ``round_tt(eps=eps or 0, rmax=rmax, algorithm=algorithm)`` brings them down, so ``eps`` bounds the
+    relative Frobenius error.  ``eps=None`` and ``rmax=None``: the exact train is returned unrounded.  When every rank of one
+    input is 1 (a separable kernel) the ranks do not grow and, for ``rmax=None``, nothing is rounded.  Tucker factors are
+    contracted in first, as the reference does.  ``mode``: ``'full'`` (``I + J - 1`` per mode), ``'same'`` (``max(I, J)``) or
+    ``'valid'`` (``max(I, J) - min(I, J) + 1``), ``np.convolve``'s windows per mode.
+
+    Unlike the reference (which multiplies the FFTs of the cores with three TT-cross runs on complex trains):
+      - the result is deterministic, real, and on the inputs' device in their dtype (fp32 or fp64);
+      - ``eps`` is ``round_tt``'s bound on the relative error, not cross's stopping criterion; the other keyword arguments of
+        ``tn.cross`` are accepted and ignored, any other keyword raises TypeError;
+      - ``'same'`` with an even smaller size starts at ``(k - 1) // 2`` as numpy does (the reference at ``k // 2``), and
+        ``'valid'`` with a smaller size of 1 returns the whole mode (the reference's slice ``[k-1 : -(k-1)]`` is empty there);
+      - different numbers of modes, devices or dtypes, batched inputs, an unknown ``mode`` and non-Tensor arguments raise
+        ValueError, CP cores NotImplementedError.
+    """
+    from ._dispatch import ops_for
+    from .tensor import Tensor, _not_in_scope
+
+    unknown = sorted(set(kwargs) - _CROSS_KWARGS)
+    if unknown:
+        raise TypeError("convolve() got an unexpected keyword argument {!r}".format(unknown[0]))
+    for t in (t1, t2):
+        if not isinstance(t, Tensor):
+            raise ValueError("convolve: expected a tntorch_amd.Tensor, got {}".format(type(t).__name__))
+        if t.batch:
+            raise ValueError("Batched tensors are not supported.")
+        if any(c.dim() == 2 for c in t.cores):
+            _not_in_scope("convolve of CP cores")
+    N = t1.dim()
+    if t2.dim() != N:
+        raise ValueError("convolve: the tensors have {} and {} modes".format(N, t2.dim()))
+    c1, c2 = t1.cores[0], t2.cores[0]
+    if c1.device != c2.device or c1.dtype != c2.dtype:
+        raise ValueError("convolve: the tensors live on {} ({}) and {} ({})".format(c1.device, c1.dtype, c2.device, c2.dtype))
+    windows = [convolve_window(I, J, mode) for I, J in zip(t1.shape, t2.shape)]
+    a = [c[0].contiguous() for c in t1._absorbed4()]
+    b = [c[0].contiguous() for c in t2._absorbed4()]
+    ops = ops_for(a[0])
+    out = Tensor([ops.core_convolve(x, y, lo, K) for x, y, (lo, K) in zip(a, b, windows)])
+    separable = all(x.shape[0] == 1 and x.shape[2] == 1 for x in a) or all(y.shape[0] == 1 and y.shape[2] == 1 for y in b)
+    if (eps is None and rmax is None) or (separable and rmax is None):
+        return out
+    out.round_tt(eps=eps or 0, rmax=rmax, algorithm=algorithm)
+    return out
