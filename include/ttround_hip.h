@@ -53,8 +53,8 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve was ADDED under 17: no existing signature changed, and a library without the
-   symbol fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve and ttr_accept_count / ttr_accept_expand were ADDED under 17: no existing signature changed, and a library without the
+   symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -907,6 +907,37 @@ int ttr_laplace_core(int dtype, int64_t R, int64_t I, int64_t C, int pos, int pe
 int ttr_core_convolve_max_taps(void);
 int ttr_core_convolve(int dtype, int64_t R1, int64_t I, int64_t R2, int64_t S1, int64_t J, int64_t S2, int64_t lo, int64_t K,
                       const void* a, const void* c, void* out, void* stream);
+
+/*
+ * Enumeration of the strings a mask accepts, level by level (added under ABI 17; automata.py:84-128 `accepted_inputs`, a Python
+ * recursion with one matmul per prefix there).  The frontier at mode mu is the productive prefixes in
+ * lexicographic order: `L` [P, r] (ALWAYS fp64: path counts are integers and stay exact up to 2^53), `off` [P] the first output
+ * row of a prefix and `cnt` [P] its number of output rows (int64).  `dtype` is that of `fiber` / `core`; both are converted to
+ * fp64 at the load and accumulated in fp64 (FMA, increasing index).  All arrays are contiguous.
+ *
+ * ttr_accept_count    C[p, i] = rint(sum_a L[p, a] fiber[a, i])  (int64 [P, I]; saturated at +-2^53), fiber [r, I] the core
+ *                     contracted with the right environment of the following modes.
+ * ttr_accept_expand   K slots, slot k the child (p, i) = divmod(idx[k], I) (`idx` int64 [K]: the row-major positions of the
+ *                     entries C > 0, increasing).  Per slot: Lnew[k, :] = L[p, :] @ core[:, i, :] (fp64 [K, rn]; `Lnew` may be
+ *                     null at the last mode: nothing is computed then), offnew[k] = childoff[p, i] (`childoff` int64 [P, I]:
+ *                     off[p] + the exclusive scan of C along i), cntnew[k] = C[p, i].  Then every row s < S of Xs (int64
+ *                     [S, N]) receives at column mu the symbol of the last slot k with offnew[k] <= s.  Children that are
+ *                     not listed are never computed.  `flag` (one int32, zeroed by the caller before the first mode) is ORed
+ *                     with TTR_ACCEPT_NEGATIVE where some C[p, i] < 0, TTR_ACCEPT_SUM_MISMATCH where sum_i C[p, i] != cnt[p]
+ *                     and TTR_ACCEPT_BAD_INDEX where an idx[k] lies outside [0, P I) (that slot is skipped).  K = 0 checks the
+ *                     parents and writes nothing else.
+ * Stores are indexed by k < K, s < S and p < P only, whatever the data.  Before any launch: TTR_E_INVALID for a bad dtype, bad
+ * sizes, a null pointer, or a rank r / rn above ttr_accept_max_rank() (= 1024: the kernels loop over r per output, untiled);
+ * TTR_E_UNSUPPORTED where the frontier does not fit the grid.  No scratch, no host synchronisation.  Profiling kind: TTR_PROF_MISC.
+ */
+#define TTR_ACCEPT_NEGATIVE 1
+#define TTR_ACCEPT_SUM_MISMATCH 2
+#define TTR_ACCEPT_BAD_INDEX 4
+int ttr_accept_max_rank(void);
+int ttr_accept_count(int dtype, int64_t P, int64_t r, int64_t I, const void* L, const void* fiber, void* C, void* stream);
+int ttr_accept_expand(int dtype, int64_t P, int64_t r, int64_t I, int64_t rn, int64_t K, int64_t N, int64_t mu, int64_t S,
+                      const void* L, const void* core, const void* C, const void* childoff, const void* cnt, const void* idx,
+                      void* Lnew, void* offnew, void* cntnew, void* Xs, void* flag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,8 @@ tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``),
 (``tn.als_completion``), sparse TT-SVD (``tn.sparse_tt_svd``), the moment family (``tn.hadamard_sum``, ``tn.raw_moment``,
 ``tn.normalized_moment``, ``tn.var``, ``tn.std``) and the differential operators of ``derivatives.py`` (``tn.partial``,
 ``tn.gradient``, ``tn.divergence``, ``tn.curl``, ``tn.laplacian``, ``tn.dgsm``, ``tn.active_subspace``) and the exact
-convolution of two trains (``tn.convolve``).
+convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automata`` (``tn.weight_mask``, ``tn.accepted_inputs``,
+...), ``tn.logic`` (``tn.symbols``, ``tn.only``, ``tn.implies``, ...), ``tn.mask`` and ``tn.partialset``.
 """
 
 from .tools import *  # noqa: F401,F403
@@ -22,6 +23,9 @@ from .cross import *  # noqa: F401,F403
 from .ops import *  # noqa: F401,F403
 from .interpolation import *  # noqa: F401,F403
 from .derivatives import *  # noqa: F401,F403
+from .automata import *  # noqa: F401,F403
+from .logic import *  # noqa: F401,F403
+from . import automata, logic  # noqa: F401
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

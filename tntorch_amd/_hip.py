@@ -1312,3 +1312,57 @@ def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Te
     out = torch.empty((R1 * S1, max(K, 0), R2 * S2), dtype=a.dtype, device=a.device)
     _call("ttr_core_convolve", dt, R1, I, R2, S1, J, S2, lo, K, a.data_ptr(), c.data_ptr(), out.data_ptr())
     return out
+
+
+def accept_max_rank() -> int:
+    """ttr_accept_max_rank: the largest rank ttr_accept_count / ttr_accept_expand take."""
+    return int(lib().ttr_accept_max_rank())
+
+
+def _accept_arg(x: torch.Tensor, dtype, shape, name: str):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and tuple(x.shape) == tuple(shape) and x.is_contiguous()):
+        raise ValueError("accept: {} must be a contiguous {} device tensor of shape {}".format(name, dtype, tuple(shape)))
+
+
+@_on_device
+def accept_count(L: torch.Tensor, fiber: torch.Tensor) -> torch.Tensor:
+    """ttr_accept_count: L [P, r] (fp64), fiber [r, I] (fp32 or fp64) -> C [P, I] int64, C = rint(L @ fiber) accumulated in fp64.
+    ValueError for a rank above accept_max_rank()."""
+    dt = dtype_code(fiber.dtype)
+    if L.dim() != 2 or fiber.dim() != 2:
+        raise ValueError("accept_count: expected L [P, r] and fiber [r, I]")
+    P, r = L.shape
+    I = fiber.shape[1]
+    _accept_arg(L, torch.float64, (P, r), "L")
+    _accept_arg(fiber, fiber.dtype, (r, I), "fiber")
+    C = torch.empty((P, I), dtype=torch.int64, device=L.device)
+    _call("ttr_accept_count", dt, P, r, I, L.data_ptr(), fiber.data_ptr(), C.data_ptr())
+    return C
+
+
+@_on_device
+def accept_expand(L: torch.Tensor, core: torch.Tensor, C: torch.Tensor, childoff: torch.Tensor, cnt: torch.Tensor, idx: torch.Tensor,
+                  Xs: torch.Tensor, mu: int, flag: torch.Tensor, last: bool):
+    """ttr_accept_expand: the K = len(idx) listed children of the frontier (L [P, r] fp64, C / childoff [P, I], cnt [P]) through
+    core [r, I, r'] -> (Lnew [K, r'] fp64 or None when ``last``, offnew [K], cntnew [K]); column ``mu`` of Xs [S, N] is filled and
+    ``flag`` (int32 [1]) ORed.  ValueError for a rank above accept_max_rank()."""
+    dt = dtype_code(core.dtype)
+    if L.dim() != 2 or core.dim() != 3 or Xs.dim() != 2 or idx.dim() != 1:
+        raise ValueError("accept_expand: expected L [P, r], core [r, I, r'], idx [K] and Xs [S, N]")
+    P, r = L.shape
+    I, rn = core.shape[1], core.shape[2]
+    K, (S, N) = idx.shape[0], Xs.shape
+    _accept_arg(L, torch.float64, (P, r), "L")
+    _accept_arg(core, core.dtype, (r, I, rn), "core")
+    _accept_arg(C, torch.int64, (P, I), "C")
+    _accept_arg(childoff, torch.int64, (P, I), "childoff")
+    _accept_arg(cnt, torch.int64, (P,), "cnt")
+    _accept_arg(idx, torch.int64, (K,), "idx")
+    _accept_arg(Xs, torch.int64, (S, N), "Xs")
+    _accept_arg(flag, torch.int32, (1,), "flag")
+    Lnew = None if last else torch.empty((K, rn), dtype=torch.float64, device=L.device)
+    offnew = torch.empty((K,), dtype=torch.int64, device=L.device)
+    cntnew = torch.empty((K,), dtype=torch.int64, device=L.device)
+    _call("ttr_accept_expand", dt, P, r, I, rn, K, N, int(mu), S, L.data_ptr(), core.data_ptr(), C.data_ptr(), childoff.data_ptr(),
+          cnt.data_ptr(), idx.data_ptr(), _ptr(Lnew), offnew.data_ptr(), cntnew.data_ptr(), Xs.data_ptr(), flag.data_ptr())
+    return Lnew, offnew, cntnew

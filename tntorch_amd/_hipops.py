@@ -2023,3 +2023,27 @@ def sparse_step(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.Tens
     q = max(1, min(cap, int(info[0].item())))                         # (readback: sizes the next core)
     W = _hip.sparse_project(V, I, colptr, blk_i, U[0], q)
     return U[0][:, :q], W
+
+
+# ---------------------------------------------------------------------------------------------- accepted inputs (automata.py:84-128)
+def accept_fibers(cores):
+    """fibers[mu] = core_mu x_3 right_{mu+1} (fp64 [r_mu, I_mu]; one ttr_gemm each), right_mu = sum_i fibers[mu][:, i], and the
+    total right_0 (fp64 [r_0])."""
+    right = torch.ones((1, cores[-1].shape[2], 1), dtype=torch.float64, device=cores[0].device)
+    fibers = []
+    for c in reversed(cores):
+        r, I, rn = c.shape
+        f = _hip.gemm(c.double().reshape(1, r * I, rn), right).reshape(r, I)
+        fibers.append(f)
+        right = f.sum(dim=1).reshape(1, r, 1)
+    return fibers[::-1], right.reshape(-1)
+
+
+def accept_count(L: torch.Tensor, fiber: torch.Tensor) -> torch.Tensor:
+    """C [P, I] = rint(L @ fiber) as int64 (ttr_accept_count)."""
+    return _hip.accept_count(L.contiguous(), fiber.contiguous())
+
+
+def accept_expand(L, core, C, childoff, cnt, idx, Xs, mu, flag, last):
+    """The listed children of one frontier through one core (ttr_accept_expand): (Lnew, offnew, cntnew); fills Xs[:, mu]."""
+    return _hip.accept_expand(L.contiguous(), core.contiguous(), C, childoff.contiguous(), cnt, idx, Xs, mu, flag, last)

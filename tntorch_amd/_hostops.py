@@ -644,3 +644,60 @@ def sparse_step(V: torch.Tensor, I: int, colptr: torch.Tensor, blk_i: torch.Tens
     rank = max(1, min(cap, kept))
     left = v[:, :rank]
     return left, _mm(left.t(), D).t().contiguous()
+
+
+# ---------------------------------------------------------------------------------------------- accepted inputs (automata.py:84-128)
+ACCEPT_NEGATIVE, ACCEPT_SUM_MISMATCH, ACCEPT_BAD_INDEX = 1, 2, 4   # include/ttround_hip.h: TTR_ACCEPT_*
+
+
+def accept_fibers(cores):
+    """fibers[mu] = core_mu x_3 right_{mu+1} (fp64 [r_mu, I_mu]), right_mu = sum_i fibers[mu][:, i], right_N = 1, and the total
+    right_0 (fp64 [r_0])."""
+    right = torch.ones((cores[-1].shape[2], 1), dtype=torch.float64, device=cores[0].device)
+    fibers = []
+    for c in reversed(cores):
+        r, I, rn = c.shape
+        f = (c.double().reshape(r * I, rn) @ right).reshape(r, I)
+        fibers.append(f)
+        right = f.sum(dim=1, keepdim=True)
+    return fibers[::-1], right[:, 0]
+
+
+def accept_count(L: torch.Tensor, fiber: torch.Tensor) -> torch.Tensor:
+    """Mirror of ttr_accept_count: C = rint(L @ fiber) in fp64, saturated at +-2^53, int64 [P, I]."""
+    v = torch.round(L.double() @ fiber.double())
+    v = torch.nan_to_num(v, nan=-2.0 ** 53).clamp(-2.0 ** 53, 2.0 ** 53)
+    return v.to(torch.int64)
+
+
+def accept_expand(L, core, C, childoff, cnt, idx, Xs, mu, flag, last):
+    """Mirror of ttr_accept_expand, level-synchronous: every listed child (p, i) = divmod(idx[k], I) at once.  Returns
+    (Lnew [K, r'] fp64 or None when ``last``, offnew [K], cntnew [K]); fills Xs[:, mu] and ORs ``flag`` (int32 [1])."""
+    P, I = C.shape
+    bits = 0
+    if bool((C < 0).any()):
+        bits |= ACCEPT_NEGATIVE
+    if bool((C.sum(dim=1) != cnt).any()):
+        bits |= ACCEPT_SUM_MISMATCH
+    ok = (idx >= 0) & (idx < P * I)
+    if not bool(ok.all()):
+        bits |= ACCEPT_BAD_INDEX
+    flag |= bits
+    K, S = idx.shape[0], Xs.shape[0]
+    pos = idx.clamp(0, P * I - 1)
+    p, i = torch.div(pos, I, rounding_mode="floor"), pos % I
+    offnew, cntnew = childoff.reshape(-1)[pos], C.reshape(-1)[pos]
+    Lnew = None
+    if not last:
+        # [K, r] x [K, r, r'] as one product per symbol: the slices core[:, i, :] are shared by every slot of that symbol
+        Lnew = torch.zeros((K, core.shape[2]), dtype=torch.float64, device=L.device)
+        cd = core.double()
+        for sym in range(I):
+            sel = torch.nonzero(i == sym).reshape(-1)
+            if sel.numel():
+                Lnew[sel] = L[p[sel]].double() @ cd[:, sym, :]
+    if K > 0 and S > 0:
+        rows = torch.arange(S, device=Xs.device)
+        k = (torch.searchsorted(offnew, rows, right=True) - 1).clamp(0, K - 1)   # the last slot with offnew[k] <= s
+        Xs[:, mu] = i[k]
+    return Lnew, offnew, cntnew

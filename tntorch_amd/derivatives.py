@@ -4,7 +4,8 @@ Mirror of ``tntorch/derivatives.py`` (``partial`` 72-130, ``gradient`` 133-157, 
 ``divergence`` 238-258, ``curl`` 261-283, ``laplacian`` 286-302).  A derivative is a stencil on ONE core (``ttr_mode_diff``);
 ``laplacian`` builds the exact rank-2r train of the sum of one-site operators (``ttr_laplace_core``) instead of adding N trains;
 ``dgsm`` / ``active_subspace`` contract left and right environments with ``ttr_hsum_step`` instead of building N gradient trains
-and N (N + 1) / 2 product trains.  ``partialset`` stays out: it needs ``automata`` and ``mask``.
+and N (N + 1) / 2 product trains.  ``partialset`` (6-69) stacks the forward differences of every mode
+behind the mode itself and selects the partials of the wanted orders with ``automata.weight_mask`` and ``tools.mask``.
 
 Unlike the reference, in every function here:
   - everything follows the input's device and dtype, fp32 or fp64 (the reference puts the ``dgsm`` / ``active_subspace`` results
@@ -14,7 +15,9 @@ Unlike the reference, in every function here:
     mode 0's extent for every mode);
   - batched tensors raise ValueError, CP cores NotImplementedError;
   - wrong lengths of ``bounds`` / ``marginals`` / ``ts``, unequal shapes, ``order < 1``, a ``dim`` out of range and a ``curl`` of
-    anything but three 3-mode tensors raise ValueError (the reference asserts, or fails further down).
+    anything but three 3-mode tensors raise ValueError (the reference asserts, or fails further down);
+  - ``partialset`` divides every difference of mode ``n`` by the same step ``(b1 - b0) / (t.shape[n] - 1)`` (the reference
+    recomputes the step from the shrinking stack, so with default bounds its second difference no longer has step 1).
 """
 
 import torch
@@ -22,7 +25,7 @@ import torch
 from ._dispatch import ops_for
 from .tensor import Tensor, _not_in_scope
 
-__all__ = ["partial", "gradient", "divergence", "curl", "laplacian", "dgsm", "active_subspace"]
+__all__ = ["partialset", "partial", "gradient", "divergence", "curl", "laplacian", "dgsm", "active_subspace"]
 
 
 # ---------------------------------------------------------------------------------------------- arguments
@@ -84,6 +87,62 @@ def _dims(t, dim, what):
             raise ValueError("{}: dim {!r} out of range for a tensor of {} modes".format(what, d, N))
         out.append(int(d) % N)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- partialset
+def partialset(t, order=1, mask=None, bounds=None):
+    """A tensor that holds all partial derivatives of certain order(s), optionally restricted by a mask (derivatives.py:6-69).
+    No padding: mode ``n`` of the result is the mode itself followed by its forward differences of order 1 .. max(order), of
+    sizes I, I - 1, ..., and ``result.idxs[n]`` gives the order of every slice.  An entry whose slices have orders
+    (o_1, .., o_N) is that mixed forward difference of ``t`` where ``sum o_n`` is in ``order`` (and ``mask`` accepts the modes
+    with ``o_n > 0``), and zero elsewhere.
+
+    >>> x, y, z = tn.symbols(3)
+    >>> tn.partialset(t, 1, x)                 # x
+    >>> tn.partialset(t, 2, x)                 # xx, xy, xz
+    >>> tn.partialset(t, 2, tn.only(y | z))    # yy, yz, zz
+
+    :param order: an int or list of ints.  Default is 1
+    :param mask: an optional 2^N mask :class:`Tensor` to select only a subset of partials
+    :param bounds: one pair [b0, b1] per mode; every difference of mode ``n`` is divided by the step ``(b1 - b0) / (I_n - 1)``.
+        Default: ``[0, I_n - 1]``, all steps 1
+
+    Unlike the reference: the step of a mode is the same for every order (see the module docstring); a mode too short for
+    ``max(order)`` differences (a mode of size 1 for any order) and batched tensors raise ValueError.
+    """
+    from .automata import weight_mask
+    from .tools import mask as apply_mask
+
+    cores = _cores3(t, "partialset")
+    N = len(cores)
+    orders = [int(o) for o in order] if hasattr(order, "__len__") else [int(order)]
+    if not orders or min(orders) < 0:
+        raise ValueError("partialset: order must be one or more non-negative integers, got {!r}".format(order))
+    max_order = max(orders)
+    if bounds is None:
+        bounds = [[0, c.shape[1] - 1] for c in cores]
+    if len(bounds) != N or not all(_is_pair(b) for b in bounds):
+        raise ValueError("partialset: bounds must be one pair [b0, b1] per mode ({}), got {!r}".format(N, bounds))
+    stacked, idxs = [], []
+    for n, core in enumerate(cores):
+        I = core.shape[1]
+        if I < 2 or I < max_order + 1:
+            raise ValueError("Tensor size {} along dimension {} not enough to compute high-order derivative".format(I, n))
+        if bounds[n][1] == bounds[n][0]:
+            raise ValueError("partialset: empty range {!r} in bounds".format(list(bounds[n])))
+        inv_step = (I - 1) / float(bounds[n][1] - bounds[n][0])
+        stack = [core]
+        for o in range(max_order):
+            stack.append((stack[-1][:, 1:, :] - stack[-1][:, :-1, :]) * inv_step)
+        stacked.append(torch.cat(stack, dim=1))
+        idxs.append(torch.cat([torch.full((s.shape[1],), o, dtype=torch.int64, device=core.device) for o, s in enumerate(stack)]))
+    d = Tensor(stacked, idxs=idxs)
+    wm = weight_mask(N, orders, nsymbols=max_order + 1, dtype=cores[0].dtype, device=cores[0].device)
+    if mask is not None:
+        wm = apply_mask(wm, mask)
+    result = apply_mask(d, wm)
+    result.idxs = idxs
+    return result
 
 
 # ---------------------------------------------------------------------------------------------- partial / gradient

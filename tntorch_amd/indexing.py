@@ -89,7 +89,7 @@ def getitem(t, key: Any):
     from .tensor import Tensor, _not_in_scope
 
     if isinstance(key, Tensor):
-        _not_in_scope("indexing with a mask Tensor (tn.accepted_inputs, automata)")
+        _not_in_scope("indexing with a mask Tensor (gather tn.accepted_inputs(mask) instead: t[tn.accepted_inputs(mask)])")
     nb = 1 if t.batch else 0
     if any(c.dim() != nb + 3 for c in t.cores):
         _not_in_scope("indexing CP cores")

@@ -444,6 +444,19 @@ class Tensor(object):
             _not_in_scope("the quotient of two tensor trains")
         return self * (1.0 / other)
 
+    # ------------------------------------------------------------------ Boolean logic (tensor.py:809-822)
+    def __invert__(self):
+        return 1 - self
+
+    def __and__(self, other):
+        return self * other
+
+    def __or__(self, other):
+        return self + other - self * other
+
+    def __xor__(self, other):
+        return self + other - 2 * self * other
+
     # ------------------------------------------------------------------ orthogonalisation (tensor.py:1771-1909)
     def left_orthogonalize(self, mu: int):
         """Make core ``mu`` left-orthogonal, push ``R`` into core ``mu+1`` (tensor.py:1800-1833)."""

@@ -1,6 +1,7 @@
 """Unfoldings of TT cores / dense tensors -- the layout contract of the hot path -- and the rounding tree.
 
-Mirror of ``tntorch/tools.py:211-258`` (same names, arguments and results), and ``convolve`` (tools.py:579-647).  All three are
+Mirror of ``tntorch/tools.py:211-258`` (same names, arguments and results), ``convolve`` (tools.py:579-647) and ``mask``
+(tools.py:333-359).  All three are
 pure ``reshape``/``permute`` views: a core ``[r0, I, r1]`` is row-major, so its left
 unfolding has row index ``r0*I + i`` and its right unfolding column index ``i*R1 + r1`` --
 exactly the addressing the HIP kernels use (no data movement on either side).
@@ -11,7 +12,7 @@ import time
 import numpy as np
 import torch
 
-__all__ = ["meshgrid", "unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode", "convolve"]
+__all__ = ["meshgrid", "unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode", "convolve", "mask"]
 
 
 def meshgrid(*axes, batch=False):
@@ -224,3 +225,38 @@ def convolve(t1, t2, mode="full", eps=1e-6, rmax=None, algorithm="svd", **kwargs
         return out
     out.round_tt(eps=eps or 0, rmax=rmax, algorithm=algorithm)
     return out
+
+
+def mask(t, mask):
+    """Masks a tensor (tools.py:333-359): the element-wise product ``t * mask``, with the mask's slices matched by their meaning --
+    slice ``j`` of mode ``n`` of ``t`` meets slice ``t.idxs[n][j]`` of the mask, clamped to the mask's size (identity indexing
+    unless ``t`` carries ``idxs``).  The selection is made on the mask's Tucker factor where it has one.  Everything runs on
+    ``t``'s device; the product is ``Tensor.__mul__`` (one ``core_kron`` per mode).
+
+    :param t: input :class:`Tensor`
+    :param mask: a mask :class:`Tensor`
+
+    :return: masked :class:`Tensor`
+    """
+    from .tensor import Tensor
+
+    for x, what in ((t, "t"), (mask, "mask")):
+        if not isinstance(x, Tensor):
+            raise ValueError("mask: {} must be a tntorch_amd.Tensor, got {}".format(what, type(x).__name__))
+        if x.batch:
+            raise ValueError("Batched tensors are not supported.")
+    if mask.dim() != t.dim():
+        raise ValueError("mask: the tensor has {} modes, the mask {}".format(t.dim(), mask.dim()))
+    device, dtype = t.cores[0].device, t.cores[0].dtype
+    cores, Us = [], []
+    for n in range(t.dim()):
+        idx = t.idxs[n] if torch.is_tensor(t.idxs[n]) else torch.as_tensor(np.asarray(t.idxs[n]))
+        idx = idx.to(device).long().clamp(max=mask.shape[n] - 1)
+        core = mask.cores[n].to(device=device, dtype=dtype)
+        if mask.Us[n] is None:
+            cores.append(core[..., idx, :])
+            Us.append(None)
+        else:
+            cores.append(core)
+            Us.append(mask.Us[n].to(device=device, dtype=dtype)[idx, :])
+    return t * Tensor(cores, Us=Us)
