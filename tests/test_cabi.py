@@ -155,6 +155,19 @@ def test_host_only_entry_points(lib):
     assert b"dtype" in lib.ttr_last_error()
 
 
+def test_one_build_recipe():
+    """csrc/Makefile is the manifest: it lists exactly the sources that exist, build() compiles exactly that list, and the
+    eigensolver keeps its measured per-file flag."""
+    import __graft_entry__ as g
+
+    csrc = os.path.join(ROOT, "tntorch_amd", "csrc")
+    text = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    src = re.search(r"^SRC\s*:=(.*)$", text, flags=re.M).group(1).split()
+    assert sorted(src) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) and len(set(src)) == len(src)
+    assert g.SOURCES == src
+    assert "-fno-slp-vectorize" in g.EXTRA_FLAGS["ttr_eigh.hip"]
+
+
 def test_no_silent_fallback_for_device_tensors(monkeypatch):
     """A CUDA tensor must never be routed to the host mirror; missing library => RuntimeError."""
     import torch

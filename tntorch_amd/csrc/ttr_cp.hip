@@ -4,6 +4,7 @@
 // Gram matrices.  HBM-streaming kernels: T is read exactly once, coalesced; no Khatri-Rao matrix and no
 // permuted unfolding copy is ever materialised.
 #include "ttr_common.h"
+#include "detail/ttr_internal.h"  // declares the dispatchers defined below
 
 namespace ttr {
 

@@ -20,6 +20,7 @@
 // only nearly orthogonal) and checks the diagonal of that R for collapsed columns (clusters / multiple eigenvalues: the caller
 // falls back to the block-Jacobi driver).
 #include "ttr_common.h"
+#include "detail/ttr_internal.h"  // declares the dispatchers defined below
 
 namespace ttr {
 
