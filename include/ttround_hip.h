@@ -53,7 +53,7 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve and ttr_accept_count / ttr_accept_expand were ADDED under 17: no existing signature changed, and a library without the
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand and ttr_mode_scan / ttr_mode_reduce were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
@@ -938,6 +938,34 @@ int ttr_accept_count(int dtype, int64_t P, int64_t r, int64_t I, const void* L, 
 int ttr_accept_expand(int dtype, int64_t P, int64_t r, int64_t I, int64_t rn, int64_t K, int64_t N, int64_t mu, int64_t S,
                       const void* L, const void* core, const void* C, const void* childoff, const void* cnt, const void* idx,
                       void* Lnew, void* offnew, void* cntnew, void* Xs, void* flag, void* stream);
+
+/*
+ * Array tools on one TT core (added under ABI 17; ops.py:6-30 `cumsum`, tools.py:266-325 `ttm` with a vector):
+ * streaming kernels, no scratch, no host synchronisation, no atomics, 64-bit indices.  A core X [R, I, C] is R slabs of a row-major
+ * [I, C] matrix (a Tucker factor [I, S] is R = 1, C = S).  Conventions of ttr_mode_diff: X is contiguous, its 3 element strides
+ * are passed as a HOST array and checked (TTR_E_UNSUPPORTED before a byte is read; the stride of an extent-1 axis is free);
+ * X == Y, an extent < 1, a bad dtype or a null X / Y / strides are TTR_E_INVALID; Y is untouched by a refused call.
+ *
+ * ttr_mode_scan    Y[r, i, c] = sum_{i' <= i} X[r, i', c].  Y has the element strides y_strides = (sr, si, 1) with si >= C and
+ *                  sr >= I si (else TTR_E_UNSUPPORTED): it can be a block of a wider core, and nothing outside the block is written.
+ * ttr_mode_reduce  Y[r, c] = scale * sum_i w[i] X[r, i, c].  `w`: [I] contiguous device elements of the dtype, or NULL (all
+ *                  ones).  Y [R, C] has the element strides y_strides = (sr, 1) with sr >= C (else TTR_E_UNSUPPORTED).
+ *
+ * A thread owns 16 bytes of consecutive c of one row when C is a multiple of that (one 16-byte load / store when the strides
+ * and the pointers allow it, else scalar ones with the same arithmetic), else one element.  The lanes of a wave cover up to 64
+ * such packs of a row and, where a row has fewer, several consecutive rows (lane = (i_sub, c): contiguous runs down to C = 1),
+ * combined by a cross-lane scan / reduction at lane distance C; the carry of a group of rows is the last row of the group before.
+ * Where there are fewer than 1024 (r, column tile) items and I is at least 16 row groups, the 16 waves of a workgroup take
+ * contiguous chunks of I of one item: the chunk totals pass through LDS and are added in chunk order (the scan reads its chunk
+ * twice, the second time from the cache); while such a launch has fewer than 256 workgroups the column tiles are halved, down to
+ * one pack, as long as every wave keeps a full row group.  Workgroups never communicate.  Both dtypes accumulate in fp64 registers and round
+ * once, at the store; the order of every sum follows from (R, I, C) and the dtype alone: the same call gives the same bits.
+ * Profiling kind: TTR_PROF_MISC.
+ */
+int ttr_mode_scan(int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, void* Y,
+                  const int64_t* y_strides, void* stream);
+int ttr_mode_reduce(int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, const void* w, double scale,
+                    void* Y, const int64_t* y_strides, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,10 @@ tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``),
 ``tn.normalized_moment``, ``tn.var``, ``tn.std``) and the differential operators of ``derivatives.py`` (``tn.partial``,
 ``tn.gradient``, ``tn.divergence``, ``tn.curl``, ``tn.laplacian``, ``tn.dgsm``, ``tn.active_subspace``) and the exact
 convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automata`` (``tn.weight_mask``, ``tn.accepted_inputs``,
-...), ``tn.logic`` (``tn.symbols``, ``tn.only``, ``tn.implies``, ...), ``tn.mask`` and ``tn.partialset``.
+...), ``tn.logic`` (``tn.symbols``, ``tn.only``, ``tn.implies``, ...), ``tn.mask`` and ``tn.partialset``, and the array tools of
+``tools.py`` and ``ops.py``: ``tn.squeeze``, ``tn.unsqueeze``, ``tn.unbind``, ``tn.cat``, ``tn.transpose``, ``tn.flip``, ``tn.pad``,
+``tn.ttm``, ``tn.generate_basis`` and ``tn.cumsum`` (marginalising a mode is ``tn.squeeze(tn.ttm(t, weights, dim))``; there is no
+``tn.sum`` / ``tn.mean``).
 """
 
 from .tools import *  # noqa: F401,F403

@@ -1290,6 +1290,34 @@ def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> 
     return out
 
 
+@_on_device
+def mode_scan(X: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_mode_scan: Y[r, i, c] = sum_{i' <= i} X[r, i', c] for X [R, I, C].  ``out``: a [R, I, C] view with element strides
+    (sr, si, 1) that receives the result (e.g. a block of a wider core); a fresh contiguous tensor when None.  X is passed with
+    the strides it has: the library refuses anything but contiguous ones."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and (out is None or (tuple(out.shape) == tuple(X.shape) and out.dtype == X.dtype and out.device == X.device))
+    R, I, C = X.shape
+    Y = out if out is not None else torch.empty((R, I, C), dtype=X.dtype, device=X.device)
+    _call("ttr_mode_scan", dt, R, I, C, X.data_ptr(), _i64(X.stride()), Y.data_ptr(), _i64(Y.stride()))
+    return Y
+
+
+@_on_device
+def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_mode_reduce: Y[r, c] = scale * sum_i w[i] X[r, i, c] for X [R, I, C]; ``w``: [I] contiguous elements of X's dtype on its
+    device, or None (all ones).  ``out``: a [R, C] view with element strides (sr, 1) that receives the result; a fresh contiguous
+    tensor when None.  X is passed with the strides it has: the library refuses anything but contiguous ones."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and (out is None or (tuple(out.shape) == (X.shape[0], X.shape[2]) and out.dtype == X.dtype and out.device == X.device))
+    R, I, C = X.shape
+    if w is not None and not (w.dim() == 1 and w.shape[0] == I and w.dtype == X.dtype and w.device == X.device and w.is_contiguous()):
+        raise ValueError("mode_reduce: w must be a contiguous vector of {} elements of X's dtype on X's device".format(I))
+    Y = out if out is not None else torch.empty((R, C), dtype=X.dtype, device=X.device)
+    _call("ttr_mode_reduce", dt, R, I, C, X.data_ptr(), _i64(X.stride()), _ptr(w), float(scale), Y.data_ptr(), _i64(Y.stride()))
+    return Y
+
+
 
 def core_convolve_max_taps() -> int:
     """ttr_core_convolve_max_taps: the terms of the sum ttr_core_convolve stages in LDS at once (longer sums are chunked)."""

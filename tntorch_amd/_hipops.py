@@ -922,16 +922,18 @@ def truncated_svd(M3, delta, eps, rmax, left_ortho, algorithm, batch):
 
 
 # ----------------------------------------------------------------------------------------------
-def mode_mul(core4: torch.Tensor, M3: torch.Tensor) -> torch.Tensor:
+def mode_mul(core4: torch.Tensor, M3: torch.Tensor, trans: bool = False) -> torch.Tensor:
     """[B, r0, S, r1] x_2 [B, a, S] -> [B, r0, a, r1] (the einsum of tensor.py:1790-1798, 1999-2002) as ONE batched GEMM
     over the B * r0 slices ``core[b, r0]`` (S x r1, contiguous where they lie) with the small matrix as the left
     operand: out[b, r0] = M[b] @ core[b, r0].  Neither the core nor the result is permuted (round 2 moved both through
-    layout copies); the a x S matrix is the only thing replicated (r0 times, KB)."""
+    layout copies); the a x S matrix is the only thing replicated (r0 times, KB).  ``trans``: the matrix is given as [B, S, a]
+    and enters the GEMM as a transposed operand (it is not copied)."""
     Bt, r0, S, r1 = core4.shape
-    a = M3.shape[1]
+    a = M3.shape[2] if trans else M3.shape[1]
     core4 = core4 if core4.is_contiguous() else core4.contiguous()
-    Mrep = M3.reshape(Bt, 1, a, S).expand(Bt, r0, a, S).reshape(Bt * r0, a, S)
-    out = _hip.gemm(Mrep, core4.reshape(Bt * r0, S, r1))  # [B * r0, a, r1]
+    rows, cols = (S, a) if trans else (a, S)
+    Mrep = M3.reshape(Bt, 1, rows, cols).expand(Bt, r0, rows, cols).reshape(Bt * r0, rows, cols)
+    out = _hip.gemm(Mrep, core4.reshape(Bt * r0, S, r1), transA=trans)  # [B * r0, a, r1]
     return out.reshape(Bt, r0, a, r1)
 
 
@@ -1702,6 +1704,19 @@ def mode_diff(X: torch.Tensor, order: int, periodic: bool, inv_step: float, out:
 def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> torch.Tensor:
     """One block core of the rank-2r Laplacian train (ttr_laplace_core): pos 0 [X D], 1 [[X, D], [0, X]], 2 [D ; X]."""
     return _hip.laplace_core(X.contiguous(), pos, periodic, inv_step)
+
+
+# ---------------------------------------------------------------------------------------------- array tools (ops.py:6-30, tools.py:266-325)
+def mode_scan(X: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.py:24-29 (ttr_mode_scan): the running sum along the middle axis of X [R, I, C]; ``out`` may be a block of a wider core
+    (element strides (sr, si, 1))."""
+    return _hip.mode_scan(X.contiguous(), out)
+
+
+def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tools.py:298-318 with a vector (ttr_mode_reduce): Y[r, c] = scale * sum_i w[i] X[r, i, c] for X [R, I, C]; ``w`` None: all
+    ones; ``out`` may be a [R, C] block of a wider matrix (element strides (sr, 1))."""
+    return _hip.mode_reduce(X.contiguous(), None if w is None else w.contiguous(), scale, out)
 
 
 # ---------------------------------------------------------------------------------------------- convolution (tools.py:579-647)

@@ -122,8 +122,11 @@ def _truncated_svd(M3, delta, eps, rmax, left_ortho, algorithm, batch, squeeze):
     return left, M2
 
 
-def mode_mul(core4: torch.Tensor, M3: torch.Tensor) -> torch.Tensor:
-    """[B, r0, S, r1] x_2 [B, a, S] -> [B, r0, a, r1] (the einsum of tensor.py:1790-1798, 1999-2002)."""
+def mode_mul(core4: torch.Tensor, M3: torch.Tensor, trans: bool = False) -> torch.Tensor:
+    """[B, r0, S, r1] x_2 [B, a, S] -> [B, r0, a, r1] (the einsum of tensor.py:1790-1798, 1999-2002); ``trans``: the matrix is
+    given as [B, S, a] (a view: it is not copied)."""
+    if trans:
+        M3 = M3.transpose(1, 2)
     if core4.shape[0] == 1:
         return torch.einsum("ijk,aj->iak", core4[0], M3[0])[None]
     return torch.einsum("bijk,baj->biak", core4, M3)
@@ -395,6 +398,29 @@ def laplace_core(X: torch.Tensor, pos: int, periodic: bool, inv_step: float) -> 
     mode_diff(X, 2, periodic, inv_step, out=out[:R, :, C:])
     if pos == 1:
         out[R:, :, C:] = X
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- array tools (ops.py:6-30, tools.py:266-325)
+def mode_scan(X: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mirror of ttr_mode_scan: the running sum along the middle axis of X [R, I, C], accumulated in fp64 and rounded once;
+    ``out`` (a [R, I, C] view) receives the result."""
+    Y = torch.cumsum(X.double(), dim=1).to(X.dtype)
+    if out is None:
+        return Y
+    out.copy_(Y)
+    return out
+
+
+def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mirror of ttr_mode_reduce: Y[r, c] = scale * sum_i w[i] X[r, i, c] for X [R, I, C] (``w`` None: all ones), accumulated in
+    fp64 and rounded once; ``out`` (a [R, C] view) receives the result."""
+    Xd = X.double()
+    Y = Xd.sum(dim=1) if w is None else torch.einsum("i,ric->rc", w.double(), Xd)
+    Y = (Y * float(scale)).to(X.dtype)
+    if out is None:
+        return Y
+    out.copy_(Y)
     return out
 
 
