@@ -653,8 +653,10 @@ int ttr_debug_set_qr_stamps(void* device_buffer);
  *                      taken by a one-wave-per-item kernel AHEAD of the launch and read by its blocks: an absorbed block returns at
  *                      once instead of staging Rm first (9 k cycles each, 16384 of them at the tail of every level-0 launch of the
  *                      metric), its partner writes the zero R block and taus for it; 0 = every block derives the decision from Rm
- *                      itself (round 5; A/B).  + 2: the level-1 launch of ttr_qr_apply_pushed does NOT idle the waves that hold the
- *                      absorbed leaves' (exactly zero) rows of a packed item (A/B; default: they load, multiply and store nothing). */
+ *                      itself (round 5; A/B).  + 2: level 1 of a packed item treats the absorbed leaves' (exactly zero) rows as ordinary
+ *                      rows, in ttr_qr_factor_pushed and ttr_qr_apply_pushed alike (A/B; default: the factor kernel runs its panel
+ *                      chain over the live half only and the apply kernel's waves on the zero rows load, multiply and store
+ *                      nothing; bit-identical results either way). */
 #define TTR_KNOB_QR_PACK_PRE 17
 /*   TTR_KNOB_EIGH_BIG_OCC  0 (default) / 3 / 2 = waves per SIMD the 64-row instance of ttr_eigh_top is built for in fp32 launches of
  *                      >= 1024 matrices (0: four waves, 128 registers, 106 spilled; 3: 168 registers; 2: 256 registers, none

@@ -99,7 +99,8 @@ void work_items(int kind, const int32_t* f1, const int32_t* f2, int64_t batch, c
 
 template <typename T>
 __global__ void work_qr_taus_kernel(const T* __restrict__ tau, int64_t nblk, int64_t nb_per_item, int NP, int64_t m, int64_t rpb, int n,
-                                    int kc, int reads_input, double* __restrict__ out_fl, double* __restrict__ out_by) {
+                                    int kc, int reads_input, const int32_t* __restrict__ live_half, double* __restrict__ out_fl,
+                                    double* __restrict__ out_by) {
   __shared__ double red[2 * kThreads / kWave];
   double a = 0.0, by = 0.0;
   const double s = (double)sizeof(T);
@@ -114,13 +115,14 @@ __global__ void work_qr_taus_kernel(const T* __restrict__ tau, int64_t nblk, int
     const int64_t b = blk % nb_per_item;
     double r = (double)(m - b * rpb < rpb ? m - b * rpb : rpb);
     if (r < 0) r = 0;
+    const double rl = (live_half && live_half[blk / nb_per_item] == 3) ? 0.5 * r : r;   // rows the launch computes on (QrLevel::live_half)
     double c = 16.0 * q;
     if (c > n) c = n;
     if (kc > 0) {
       a += 4.0 * r * c * kc;
       by += s * (r * c + (q > 0 ? r * kc : 0.0));                       // live reflectors read, the block's output rows written
     } else {
-      a += 2.0 * r * c * c - 2.0 * c * c * c / 3.0 + 4.0 * r * c * (n - c);
+      a += 2.0 * rl * c * c - 2.0 * c * c * c / 3.0 + 4.0 * rl * c * (n - c);
       by += s * (r * c + (q > 0 ? (double)n * n : 0.0) + (reads_input ? r * n : 0.0));   // reflectors + R written (+ the block read)
     }
   }
@@ -135,7 +137,7 @@ __global__ void work_qr_taus_kernel(const T* __restrict__ tau, int64_t nblk, int
 }
 
 void work_qr_taus(int kind, const void* tau, bool f64, int64_t nblk, int64_t nb_per_item, int NP, int64_t m, int64_t rpb, int n,
-                  int kc, bool reads_input, hipStream_t s) {
+                  int kc, bool reads_input, hipStream_t s, const int32_t* live_half) {
   if (!work_census_on() || nblk <= 0) return;
   int64_t gx = ceil_div(nblk, kThreads);
   if (gx > 512) gx = 512;
@@ -143,10 +145,10 @@ void work_qr_taus(int kind, const void* tau, bool f64, int64_t nblk, int64_t nb_
   double* by = g_work_dev + TTR_PROF_NKINDS + kind;
   if (f64)
     hipLaunchKernelGGL(work_qr_taus_kernel<double>, dim3((unsigned)gx), dim3(kThreads), 0, s, (const double*)tau, nblk, nb_per_item, NP, m,
-                       rpb, n, kc, reads_input ? 1 : 0, fl, by);
+                       rpb, n, kc, reads_input ? 1 : 0, live_half, fl, by);
   else
     hipLaunchKernelGGL(work_qr_taus_kernel<float>, dim3((unsigned)gx), dim3(kThreads), 0, s, (const float*)tau, nblk, nb_per_item, NP, m,
-                       rpb, n, kc, reads_input ? 1 : 0, fl, by);
+                       rpb, n, kc, reads_input ? 1 : 0, live_half, fl, by);
 }
 
 }  // namespace ttr

@@ -52,8 +52,9 @@ void work_items(int kind, const int32_t* f1, const int32_t* f2, int64_t batch, c
 // with r = the block's rows: rpb, the last block of an item (nb blocks per item, m rows) what is left
 // bytes: live reflectors (r c) + R (n^2) written by a factoring block, + its r x n input when `reads_input` (every launch but
 // the fused push, whose core / Rm reads are charged per item); an applying block reads its live reflectors and writes r x kc
+// live_half (factor, optional): per-item flags; a block of an item flagged 3 computes on half its rows (QrLevel::live_half)
 void work_qr_taus(int kind, const void* tau, bool f64, int64_t nblk, int64_t nb_per_item, int NP, int64_t m, int64_t rpb, int n,
-                  int kc, bool reads_input, hipStream_t s);
+                  int kc, bool reads_input, hipStream_t s, const int32_t* live_half = nullptr);
 
 // ------------------------------------------------------------------ MFMA 16x16x4 wrappers
 // A operand: lane l holds A[i = l & 15][k = l >> 4]; B operand: B[k = l >> 4][j = l & 15].

@@ -92,6 +92,12 @@ struct QrLevel {
   // block of every CU under round-robin dispatch -- start that much later, so that one block's HBM phase (the push) runs under
   // the other's panel chain instead of beside its push.
   int stagger_kc;
+  // Level 1 above a PACKED pushed level 0 (8 leaf blocks, TTR_KNOB_QR_PACK = 3): the leaf flags -- rows >= m / 2 of a flagged item
+  // are the absorbed leaves' R blocks, exactly zero: the NQL = NW / 2 instance of the kernel factors the upper half only and stores
+  // zero reflector rows for the rest.  The level is launched twice, with the half and with the full instance; a block returns at
+  // once when its item is not of the launch's kind.  The same flags, under the same predicate, as QrApply::half_zero.  nullptr
+  // otherwise.
+  const int32_t* live_half;
 };
 
 // beta = -sign(alpha) sqrt(alpha^2 + ss), tau = (beta - alpha)/beta, scale = 1/(alpha - beta)  (LAPACK larfg).
@@ -142,8 +148,20 @@ __device__ __forceinline__ void block_of(int grid_swap, int nb, int& b, int64_t&
   }
 }
 
-template <typename T, int NT, bool PUSHED, int NW, bool PAIR>
+// NQL (live rows; PAIR kernel): only the first NQL of the block's NW 64-row groups can hold a nonzero -- a short block (320 of 512
+// rows), or level 1 of a packed item (QrLevel::live_half).  The rows below are exact zeros and stay so (0 * x, x + 0): in the
+// column-owning layout nobody multiplies them, and a wave whose own 64 rows are dead (wave >= NQL) skips its share of the MFMA
+// phases.  Sums keep their order over the live terms, so the result is bit-identical to carrying the zeros along.  A template
+// parameter, chosen by the host per launch (factor_launch): a runtime bound puts a branch into every unrolled loop of the step
+// chain, and several compile-time variants inside ONE kernel spill (hipcc: 95 - 440 spilled registers for two to four variants
+// of the 64-column instances, none for any single one).
+// NOT for the single-step kernels (PAIR = false), and at least two row pairs: their scalar dot-product chains
+// (d += x[q] * c[q], then the wave reduction) are contracted differently by hipcc when the chain is shorter -- measured: R of a
+// 64-row block differs from its zero-padded twin's in the last digits (fp32 and fp64), while the pair kernel's packed chains,
+// which always end in a fused multiply-add before the horizontal add, compare equal.
+template <typename T, int NT, bool PUSHED, int NW, bool PAIR, int NQL = NW>
 __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_kernel(QrLevel<T> p) {
+  static_assert(NQL == NW || (PAIR && !PUSHED && NQL >= 4 && NQL < NW && (NQL & 1) == 0), "live 64-row groups of the block");
   using M = Mfma<T>;
   using Acc = typename M::Acc;
   typedef T V2 __attribute__((ext_vector_type(2)));  // fp32: v_pk_mul / v_pk_fma operands (two rows per instruction)
@@ -556,6 +574,10 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
     }
     lds_barrier();  // Rs aliases Vs
   } else {
+    // level 1 of packed and unpacked items: one launch of the half-block instance, one of the full one; each item is taken by one
+    if constexpr (PAIR) {
+      if (p.live_half && (p.live_half[bt] == 3) != (NQL < NW)) return;
+    }
     const T* __restrict__ X = p.X + bt * p.strideX + row0 * p.ldx;
 #pragma unroll
     for (int tm = 0; tm < 4; ++tm)
@@ -720,6 +742,13 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
   // Panels are expanded at compile time as well (acc[tm][pnl] must be a static register index).
   auto panel = [&](auto PN) {
     constexpr int pnl = decltype(PN)::value;
+    const bool wlive = NQL == NW || wave_id < NQL;   // (wave-uniform) this wave's rows are live
+    // the block-wide sum of the live waves' partials, in the association of the full sum: (0 + 1) + (2 + 3), then + ((4 + 5) + (6 + 7))
+    auto live_sum = [&](auto&& at) {
+      T s = (at(0) + at(1)) + (at(2) + at(3));
+      if constexpr (NQL > 4) { T u = at(4) + at(5); if constexpr (NQL > 6) u += at(6) + at(7); s += u; }
+      return s;
+    };
     const int j0 = pnl * PW;
     int nsteps = kb - j0;
     nsteps = nsteps < 0 ? 0 : (nsteps > PW ? PW : nsteps);
@@ -736,30 +765,48 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
     // PAIR: no barrier before this store -- the previous panel's update only reads the wave's OWN rows of Vs (A operand of
     // A2 += V W2), which are the rows it rewrites here; the single-step variant's owners write other waves' rows early
     if constexpr (!PAIR) { if (pnl > 0) lds_barrier(); }  // the previous panel's MFMA update may still be reading Vs
+    if (wlive) {   // (a dead wave's rows of the panel image are never read)
 #pragma unroll
-    for (int tm = 0; tm < 4; ++tm)
+      for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Vs[rowl(tm, r) * VLD + cl] = acc[tm][pnl][r];
+        for (int r = 0; r < 4; ++r) Vs[rowl(tm, r) * VLD + cl] = acc[tm][pnl][r];
+    }
     if constexpr (PAIR) {  // S and T of this panel are assembled during the phases (below): start from zero
       if (tid < PW * PW) { Ts[(tid >> 4) * VLD + (tid & 15)] = T(0); Ss[(tid >> 4) * VLD + (tid & 15)] = T(0); }
     }
     lds_barrier();
     bool rank_skip = false;
+    constexpr int NHL = NQL / 2;   // PAIR: live row pairs
+    // Dot product of two columns over the live row pairs, as a V2 of partial sums (the caller adds .x and .y).  The order of the
+    // fused multiply-adds is SPELLED OUT: hipcc contracts  x[0] y[0] + x[1] y[1] + ...  into a multiply and a chain of fmas, and
+    // which product becomes the multiply depended on the site and on the length of the chain -- an instance with fewer live
+    // pairs then rounded differently from the full one on the same data (R differed from the zero-padded twin's in the last
+    // digits).  FIRST = the product that is rounded on its own; the rest are fused in ascending order.  The values per site are the
+    // order the 64-column fp32 instances were compiled to before the order was spelled out (same bits as before).
+    auto dotp = [&](auto FIRST, const V2 (&x)[NW / 2], const V2 (&y)[NW / 2]) -> V2 {
+      constexpr int a = decltype(FIRST)::value, b = 1 - a;
+      V2 e = x[a] * y[a];
+      e = __builtin_elementwise_fma(x[b], y[b], e);
+#pragma unroll
+      for (int h = 2; h < NHL; ++h) e = __builtin_elementwise_fma(x[h], y[h], e);
+      return e;
+    };
     if constexpr (PAIR) {
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
-        for (int q = 0; q < NW; ++q) pcv[cc][q >> 1][q & 1] = Vs[(lane + 64 * q) * VLD + wave * 2 + cc];
+        for (int q = 0; q < NQL; ++q) pcv[cc][q >> 1][q & 1] = Vs[(lane + 64 * q) * VLD + wave * 2 + cc];
       // what is left of this panel: rows >= j0 of its columns (rows < 64 only exist in the first half of pair 0)
       {
         T e = T(0);
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
-          V2 x0 = pcv[cc][0];
-          if (lane < j0) x0.x = T(0);
-          V2 a2 = x0 * x0;
+          V2 xl[NW / 2];
+          xl[0] = pcv[cc][0];
+          if (lane < j0) xl[0].x = T(0);
 #pragma unroll
-          for (int h = 1; h < NW / 2; ++h) a2 = pcv[cc][h] * pcv[cc][h] + a2;
+          for (int h = 1; h < NHL; ++h) xl[h] = pcv[cc][h];
+          const V2 a2 = dotp(IC<0>{}, xl, xl);
           e += a2.x + a2.y;
         }
         e = wave_sum_dpp(e);
@@ -777,6 +824,11 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
       for (int cc = 0; cc < CPW; ++cc)
 #pragma unroll
         for (int q = 0; q < NW; ++q) pc[cc][q] = Vs[(lane + 64 * q) * VLD + wave * CPW + cc];
+    }
+    // workspace contract: the reflectors' rows in dead groups are stored, as zeros -- by the dead waves themselves, off the chain
+    if (!wlive && !rank_skip) {
+#pragma unroll
+      for (int j = 0; j < PW; ++j) Vt[(int64_t)(j0 + j) * BR + tid] = T(0);
     }
     // (PAIR: the owners store their reflectors to Vs only after their phase barrier, which every wave reaches after this read)
     if constexpr (!PAIR) lds_barrier();  // all columns are in registers before reflectors start overwriting Vs
@@ -824,6 +876,33 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
       // keep the columns in two register sets and copy all 16 values back and forth in every phase.
       static_assert(!PAIR || (CPW == 2 && NW == 8), "PAIR: two columns per wave, eight waves");
       constexpr int NH = NW / 2;
+      // the exchange slot of a lane: v0's pairs in words 0 .. 7, v1's in words 8 .. 15; only the pieces that hold live pairs travel
+      auto xput = [&](T* xs, const V2 (&a)[NH], const V2 (&c)[NH]) {
+        V4* const xw = reinterpret_cast<V4*>(xs);
+        xw[0] = V4{a[0].x, a[0].y, a[1].x, a[1].y};
+        xw[2] = V4{c[0].x, c[0].y, c[1].x, c[1].y};
+        if constexpr (NHL == 4) {
+          xw[1] = V4{a[2].x, a[2].y, a[3].x, a[3].y};
+          xw[3] = V4{c[2].x, c[2].y, c[3].x, c[3].y};
+        } else if constexpr (NHL == 3) {
+          *reinterpret_cast<V2*>(xs + 4) = a[2];
+          *reinterpret_cast<V2*>(xs + 12) = c[2];
+        }
+      };
+      auto xget = [&](const T* xs, V2 (&a)[NH], V2 (&c)[NH]) {
+        const V4* const xr = reinterpret_cast<const V4*>(xs);
+        const V4 r0 = xr[0], r2 = xr[2];
+        a[0] = V2{r0.x, r0.y}; a[1] = V2{r0.z, r0.w};
+        c[0] = V2{r2.x, r2.y}; c[1] = V2{r2.z, r2.w};
+        if constexpr (NHL == 4) {
+          const V4 r1 = xr[1], r3 = xr[3];
+          a[2] = V2{r1.x, r1.y}; a[3] = V2{r1.z, r1.w};
+          c[2] = V2{r3.x, r3.y}; c[3] = V2{r3.z, r3.w};
+        } else if constexpr (NHL == 3) {
+          a[2] = *reinterpret_cast<const V2*>(xs + 4);
+          c[2] = *reinterpret_cast<const V2*>(xs + 12);
+        }
+      };
       const int nph = (nsteps + 1) >> 1;            // phases = column pairs that take a step (block-uniform)
       const bool mine = wave_id < nph;
       const int napply = mine ? wave_id : nph;
@@ -839,23 +918,17 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
         lds_barrier();  // the owner's pair (exchange slot), its taus and v0^T v1 are visible
         TTR_WSTAMP(pnl, 4 * owv + 2);
         if (live) {     // apply H1 H0 to the two columns
-            const V4* const xr = reinterpret_cast<const V4*>(xb);
-            const V4 r0 = xr[0], r1 = xr[1], r2 = xr[2], r3 = xr[3];
-            const V2 w0[NH] = {V2{r0.x, r0.y}, V2{r0.z, r0.w}, V2{r1.x, r1.y}, V2{r1.z, r1.w}};
-            const V2 w1[NH] = {V2{r2.x, r2.y}, V2{r2.z, r2.w}, V2{r3.x, r3.y}, V2{r3.z, r3.w}};
+            V2 w0[NH], w1[NH];
+            xget(xb, w0, w1);
             const T ta = taus[jj], tb = taus[jj1], t12 = pairt[owv];
-            V2 e0 = w0[0] * pcv[0][0], e1 = w0[0] * pcv[1][0], e2 = w1[0] * pcv[0][0], e3 = w1[0] * pcv[1][0];
-#pragma unroll
-            for (int h = 1; h < NH; ++h) {
-              e0 = w0[h] * pcv[0][h] + e0; e1 = w0[h] * pcv[1][h] + e1;
-              e2 = w1[h] * pcv[0][h] + e2; e3 = w1[h] * pcv[1][h] + e3;
-            }
+            const V2 e0 = dotp(IC<1>{}, w0, pcv[0]), e1 = dotp(IC<1>{}, w0, pcv[1]);
+            const V2 e2 = dotp(IC<1>{}, w1, pcv[0]), e3 = dotp(IC<1>{}, w1, pcv[1]);
             T d4[4] = {e0.x + e0.y, e1.x + e1.y, e2.x + e2.y, e3.x + e3.y};
             wave_sum4(d4);
             const T a0a = ta * d4[0], a0b = ta * d4[1];
             const T a1a = tb * (d4[2] - t12 * a0a), a1b = tb * (d4[3] - t12 * a0b);
 #pragma unroll
-            for (int h = 0; h < NH; ++h) {
+            for (int h = 0; h < NHL; ++h) {
               pcv[0][h] = (pcv[0][h] - a0a * w0[h]) - a1a * w1[h];
               pcv[1][h] = (pcv[1][h] - a0b * w0[h]) - a1b * w1[h];
             }
@@ -876,10 +949,8 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
             x0[0] = pcv[0][0];
             if (!(lane > jj)) x0[0].x = T(0);
 #pragma unroll
-            for (int h = 1; h < NH; ++h) x0[h] = pcv[0][h];
-            V2 e00 = x0[0] * x0[0], e01 = x0[0] * pcv[1][0];
-#pragma unroll
-            for (int h = 1; h < NH; ++h) { e00 = x0[h] * x0[h] + e00; e01 = x0[h] * pcv[1][h] + e01; }
+            for (int h = 1; h < NHL; ++h) x0[h] = pcv[0][h];
+            const V2 e00 = dotp(IC<0>{}, x0, x0), e01 = dotp(IC<1>{}, x0, pcv[1]);
             T s00 = e00.x + e00.y, s01 = e01.x + e01.y;
             wave_sum2(s00, s01);
             const T alpha0 = lane_get(pcv[0][0].x, jj);
@@ -887,12 +958,12 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
             if (s00 < Num<T>::larfg_floor()) { beta0 = alpha0; t0 = T(0); sc0 = T(0); }  // LAPACK larfg: H = I (x = 0, or below 2^-50 of the block)
             else larfg_scalars(alpha0, s00, beta0, t0, sc0);
 #pragma unroll
-            for (int h = 0; h < NH; ++h) v0[h] = x0[h] * sc0;
+            for (int h = 0; h < NHL; ++h) v0[h] = x0[h] * sc0;
             if (!(lane > jj)) v0[0].x = (lane == jj) ? T(1) : T(0);
             {  // H0 on column 1: v0^T c1 = sc0 * x0^T c1 + c1[jj]
               const T f = t0 * (sc0 * s01 + lane_get(pcv[1][0].x, jj));
 #pragma unroll
-              for (int h = 0; h < NH; ++h) pcv[1][h] = pcv[1][h] - f * v0[h];
+              for (int h = 0; h < NHL; ++h) pcv[1][h] = pcv[1][h] - f * v0[h];
             }
             if (lane == jj) pcv[0][0].x = beta0;  // R[jj][jj]
             // ---- column 1: ||x1||^2 and v0 . x1 (for v0^T v1) in one 2-value reduction
@@ -902,10 +973,8 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
               x1[0] = pcv[1][0];
               if (!(lane > jj1)) x1[0].x = T(0);
 #pragma unroll
-              for (int h = 1; h < NH; ++h) x1[h] = pcv[1][h];
-              V2 e11 = x1[0] * x1[0], e0v = v0[0] * x1[0];
-#pragma unroll
-              for (int h = 1; h < NH; ++h) { e11 = x1[h] * x1[h] + e11; e0v = v0[h] * x1[h] + e0v; }
+              for (int h = 1; h < NHL; ++h) x1[h] = pcv[1][h];
+              const V2 e11 = dotp(IC<0>{}, x1, x1), e0v = dotp(IC<0>{}, v0, x1);
               T s11 = e11.x + e11.y, s0v = e0v.x + e0v.y;
               wave_sum2(s11, s0v);
               const T alpha1 = lane_get(pcv[1][0].x, jj1);
@@ -913,20 +982,16 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
               if (s11 < Num<T>::larfg_floor()) { beta1 = alpha1; t1 = T(0); sc1 = T(0); }
               else larfg_scalars(alpha1, s11, beta1, t1, sc1);
 #pragma unroll
-              for (int h = 0; h < NH; ++h) v1[h] = x1[h] * sc1;
+              for (int h = 0; h < NHL; ++h) v1[h] = x1[h] * sc1;
               if (!(lane > jj1)) v1[0].x = (lane == jj1) ? T(1) : T(0);
               t12 = sc1 * s0v + lane_get(v0[0].x, jj1);  // v1 = sc1 * x1 below row jj1, 1 on it
               if (lane == jj1) pcv[1][0].x = beta1;
             } else {
 #pragma unroll
-              for (int h = 0; h < NH; ++h) v1[h] = V2{T(0), T(0)};
+              for (int h = 0; h < NHL; ++h) v1[h] = V2{T(0), T(0)};
             }
-            // publish the pair: four 16-byte stores per lane
-            V4* const xw = reinterpret_cast<V4*>(xb);
-            xw[0] = V4{v0[0].x, v0[0].y, v0[1].x, v0[1].y};
-            xw[1] = V4{v0[2].x, v0[2].y, v0[3].x, v0[3].y};
-            xw[2] = V4{v1[0].x, v1[0].y, v1[1].x, v1[1].y};
-            xw[3] = V4{v1[2].x, v1[2].y, v1[3].x, v1[3].y};
+            // publish the pair: four 16-byte stores per lane (fewer when not all row pairs are live)
+            xput(xb, v0, v1);
             if (lane == 0) { taus[jj] = t0; taus[jj1] = t1; pairt[owv] = t12; }
         }
         TTR_WSTAMP(pnl, 4 * owv + 1);
@@ -937,7 +1002,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
             // image the MFMA phases read, and to the workspace (transposed: 256 contiguous bytes per store)
             // (read back from the exchange slot: keeping the pair in registers across the barrier costs spills)
 #pragma unroll
-            for (int q = 0; q < NW; ++q) {
+            for (int q = 0; q < NQL; ++q) {   // (rows of dead groups: zeros, stored by the dead waves)
               const T a = xb[q], c = xb[NW + q];
               Vs[(lane + 64 * q) * VLD + j] = a;
               Vs[(lane + 64 * q) * VLD + j + 1] = c;
@@ -962,25 +1027,14 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
         // (the wave's own pair stays in registers for the S blocks: its columns are final, so the registers are free -- re-reading
         // it from the panel image cost 16 LDS reads per phase)
         V2 u0[NH], u1[NH];
-        {
-          const V4* const xo = reinterpret_cast<const V4*>(xb);
-          const V4 o0 = xo[0], o1 = xo[1], o2 = xo[2], o3 = xo[3];
-          u0[0] = V2{o0.x, o0.y}; u0[1] = V2{o0.z, o0.w}; u0[2] = V2{o1.x, o1.y}; u0[3] = V2{o1.z, o1.w};
-          u1[0] = V2{o2.x, o2.y}; u1[1] = V2{o2.z, o2.w}; u1[2] = V2{o3.x, o3.y}; u1[3] = V2{o3.z, o3.w};
-        }
+        xget(xb, u0, u1);
         for (int k = owv + 1; k < nph; ++k) {
           lds_barrier();
           {
-            const V4* const xr = reinterpret_cast<const V4*>(Xp + (k & 1) * (64 * XLD) + lane * XLD);
-            const V4 r0 = xr[0], r1 = xr[1], r2 = xr[2], r3 = xr[3];
-            const V2 w0[NH] = {V2{r0.x, r0.y}, V2{r0.z, r0.w}, V2{r1.x, r1.y}, V2{r1.z, r1.w}};
-            const V2 w1[NH] = {V2{r2.x, r2.y}, V2{r2.z, r2.w}, V2{r3.x, r3.y}, V2{r3.z, r3.w}};
-            V2 e0 = u0[0] * w0[0], e1 = u0[0] * w1[0], e2 = u1[0] * w0[0], e3 = u1[0] * w1[0];
-#pragma unroll
-            for (int h = 1; h < NH; ++h) {
-              e0 = u0[h] * w0[h] + e0; e1 = u0[h] * w1[h] + e1;
-              e2 = u1[h] * w0[h] + e2; e3 = u1[h] * w1[h] + e3;
-            }
+            V2 w0[NH], w1[NH];
+            xget(Xp + (k & 1) * (64 * XLD) + lane * XLD, w0, w1);
+            const V2 e0 = dotp(IC<1>{}, u0, w0), e1 = dotp(IC<1>{}, u0, w1);
+            const V2 e2 = dotp(IC<1>{}, u1, w0), e3 = dotp(IC<1>{}, u1, w1);
             T d4[4] = {e0.x + e0.y, e1.x + e1.y, e2.x + e2.y, e3.x + e3.y};
             wave_sum4(d4);
             if (lane == 0) {
@@ -1178,7 +1232,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
     // depend on T: it is formed in the same barrier interval as the (serial, 16-lane) larft recurrence above, so
     // the other waves' MFMAs run under wave 0's recurrence instead of waiting for it.
     const bool trailing = pnl < NT - 1 && (pnl + 1) * PW < n && !rank_skip;   // (H = I: nothing to update)
-    if (trailing) {
+    if (trailing && wlive) {   // (a dead wave's rows of A2 are zero: no partial)
 #pragma unroll
       for (int tn = pnl + 1; tn < NT; ++tn) {
         Acc wa = M::zero();
@@ -1201,9 +1255,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
         constexpr int ncols = NP - (pnl + 1) * PW > 0 ? NP - (pnl + 1) * PW : 1;  // (> 0 whenever `trailing`)
         for (int e = tid; e < PW * ncols; e += NTH) {
           const int k = e / ncols, jc = c0 + e % ncols;
-          T acc_w = (Wp[0][k][jc] + Wp[1][k][jc]) + (Wp[2][k][jc] + Wp[3][k][jc]);
-          if constexpr (NW == 8) acc_w += (Wp[4][k][jc] + Wp[5][k][jc]) + (Wp[6][k][jc] + Wp[7][k][jc]);
-          Wp[0][k][jc] = acc_w;
+          Wp[0][k][jc] = live_sum([&](int w) { return Wp[w][k][jc]; });
         }
         lds_barrier();
         for (int e = tid; e < PW * ncols; e += NTH) {
@@ -1215,15 +1267,17 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
         }
       }
       lds_barrier();
-      // (7) A2 += V W2
+      // (7) A2 += V W2  (a dead wave's rows of V and of A2 are zero)
+      if (wlive) {
 #pragma unroll
-      for (int tn = pnl + 1; tn < NT; ++tn)
+        for (int tn = pnl + 1; tn < NT; ++tn)
 #pragma unroll
-        for (int tm = 0; tm < 4; ++tm)
+          for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-            acc[tm][tn] = M::mma(Vs[(wave * 64 + tm * 16 + cl) * VLD + ks * 4 + g], W2s[ks * 4 + g][tn * PW + cl],
-                                 acc[tm][tn]);
+            for (int ks = 0; ks < 4; ++ks)
+              acc[tm][tn] = M::mma(Vs[(wave * 64 + tm * 16 + cl) * VLD + ks * 4 + g], W2s[ks * 4 + g][tn * PW + cl],
+                                   acc[tm][tn]);
+      }
     }
     stamp();
     // the next panel's first barrier orders (7)'s LDS reads before Vs / W2s are rewritten
@@ -1752,9 +1806,25 @@ __global__ __launch_bounds__(512) void pack_flags_kernel(const T* __restrict__ R
   }
 }
 
-int g_qr_l1_idle = 1;     // (round 6) level-1 apply of packed items: waves 4 .. 7 idle (QrApply::half_zero); 0 with TTR_KNOB_QR_PACK_PRE = 2 (A/B)
+int g_qr_l1_idle = 1;     // level 1 of packed items: the absorbed leaves' zero rows are skipped by the factor kernel (QrLevel::live_half) and by
+                          // the apply kernel (QrApply::half_zero: waves 4 .. 7 idle); 0 with bit 1 of TTR_KNOB_QR_PACK_PRE: ordinary rows (A/B)
 int g_qr_pack_pre_min = 256;   // smallest batch that takes the packing decision ahead of the launch
 int g_qr_pack_pre = 1;   // ttr_debug_set_knob(TTR_KNOB_QR_PACK_PRE): 0 = every block derives the packing decision from Rm itself (round 5)
+
+// Level 1 of a two-level tree above a pushed level 0 whose items may have PACKED their rows (TTR_KNOB_QR_PACK = 3: the leaves
+// b >= nb / 2 of a packed item are absorbed and write a zero R): the per-item leaf flags (workspace, off_flag) tell the level-1
+// factor and apply kernels that rows >= 256 of the item's 512 stacked rows are exactly zero.  One predicate for both sides.
+static bool l1_half_zero(const QrPlan& pl, int l, int n, bool pushed) {
+  return l == 1 && pl.levels == 2 && pushed && g_qr_pack == 3 && g_qr_l1_idle && pl.nb[0] == 8 && pl.nw[1] == 8 && n == 64 && pl.m[1] == 512;
+}
+
+// A plain (not pushed) level on the 8-wave pair kernel: the instance for `nlq` live quarters of the 512-row block (1 .. 4)
+template <typename T, int NT>
+static void factor_launch(int nlq, dim3 grid, hipStream_t stream, const QrLevel<T>& p) {
+  if (nlq >= 4) hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 8>), grid, dim3(512), 0, stream, p);
+  else if (nlq == 3) hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 6>), grid, dim3(512), 0, stream, p);
+  else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 4>), grid, dim3(512), 0, stream, p);
+}
 
 template <typename T, int NT>
 static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, int64_t strideA, T* R, int64_t ldr,
@@ -1781,6 +1851,10 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
     p.top = (l == L - 1);
     p.expo_acc = (p.top && !(l == 0 && pu.Rm)) ? pu.expo_acc : nullptr;
     p.stagger_kc = g_qr_stagger;
+    // (from g_qr_pack_pre_min items on, like the packing decision ahead of the launch: the level then costs two launches, one of
+    // which only returns -- in a latency-bound small-batch sweep that launch costs what the shorter chain saves)
+    p.live_half = (l1_half_zero(pl, l, n, pu.Rm != nullptr) && g_qr_variant != 0 && batch >= g_qr_pack_pre_min)
+                      ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
     if (p.top) { p.Rout = R; p.ldr = ldr; p.strideR = strideR; }
     else { p.Rout = ws + pl.off_x[l + 1]; p.ldr = n; p.strideR = pl.m[l + 1] * n; }
     const bool pushed = (l == 0 && pu.Rm);
@@ -1798,9 +1872,13 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
                            pu.strideRm, pu.Rin, batch, g_rank_skip_c, p.pack_ok, p.pack_flag);
       p.grid_swap = (p.pack_ok == 3 && l == 0 && pu.Rm) ? ((g_qr_interleave && (pl.nb[l] & 1) == 0) ? 2 : 1) : 0;
       const dim3 grid = p.grid_swap ? dim3((unsigned)batch, (unsigned)pl.nb[l]) : dim3((unsigned)pl.nb[l], (unsigned)batch);
+      // live quarters of this level's blocks (the longest block: rows beyond a shorter one's are loaded as zeros)
+      const int64_t rows_max = ceil_div(pl.m[l], (int64_t)pl.nb[l]);
+      const int nlq = (int)ceil_div(rows_max, (int64_t)16 * pl.nw[l]);
       if (pl.nw[l] == 8 && g_qr_variant != 0) {
         if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, true>), grid, dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true>), grid, dim3(512), 0, stream, p);
+        else if (p.live_half) { factor_launch<T, NT>(2, grid, stream, p); factor_launch<T, NT>(4, grid, stream, p); }   // packed items, the rest
+        else factor_launch<T, NT>(nlq, grid, stream, p);
       } else if (pl.nw[l] == 8) {
         if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, false>), grid, dim3(512), 0, stream, p);
         else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, false>), grid, dim3(512), 0, stream, p);
@@ -1810,7 +1888,8 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
       }
     }
     if (work_census_on()) {   // what this launch executed, from the taus / flags it left behind (outside the timed scope)
-      work_qr_taus(TTR_PROF_QR_FACTOR, p.tau, sizeof(T) == 8, batch * pl.nb[l], pl.nb[l], pl.npad, pl.m[l], 64 * pl.nw[l], n, 0, !pushed, stream);
+      work_qr_taus(TTR_PROF_QR_FACTOR, p.tau, sizeof(T) == 8, batch * pl.nb[l], pl.nb[l], pl.npad, pl.m[l], 64 * pl.nw[l], n, 0, !pushed, stream,
+                   p.live_half);
       if (pushed) {
         // the fused push Rm (k x Rin) x core (Rin x I n): 16 x 16 (row tile, K group) products; an upper-triangular Rm skips the
         // tiles below the diagonal (square Rm: T (T + 1) / 2 of T^2); a packed item only forms rows 0 .. 31 (7 of its 8 tiles)
@@ -1855,8 +1934,7 @@ static int apply_run(int64_t m, int n, int64_t batch, const T* ws, T* wsw, const
     p.pk = (l == 0) ? pk : 0; p.pI = (l == 0) ? pI : 0;
     p.Gp = (l == 0) ? Gp : nullptr;
     p.pack_flag = (l == 0 && pk > 0) ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
-    p.half_zero = (l == 1 && L == 2 && pk > 0 && g_qr_pack == 3 && g_qr_l1_idle && pl.nb[0] == 8 && pl.nw[1] == 8 && n == 64 && pl.m[1] == 512)
-                      ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
+    p.half_zero = l1_half_zero(pl, l, n, pk > 0) ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
     p.skip_zero_rows = (l == 0) ? skipz : 0;
     p.dbg = (l == 0) ? g_qr_dbg : nullptr;
     {
