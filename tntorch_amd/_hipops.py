@@ -37,7 +37,7 @@ from __future__ import annotations
 import math
 import os
 import time
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -453,24 +453,24 @@ def _subspace_basis(G: torch.Tensor, r: int) -> Optional[torch.Tensor]:
     return None
 
 
-def _subspace_truncate(M, G, r, delta, rmax, left_ortho, algorithm, batch, right_alloc, gtr):
+def _subspace_truncate(M, G, cut, delta, right_alloc, gtr):
     """``truncate`` of a big bond through the range finder above; None when the basis is not certified (or, in eps mode, the
     rank rule does not return the cap on the visible spectrum)."""
     Bt, m, n = M.shape
     left_side = m <= n
+    r = cut.rcap
     Q = _subspace_basis(G, r)
     if Q is None:
         return None
     if left_side:
         Bm = _hip.gemm(Q, M, transA=True)                 # l x n: the fused row kernels take it from here
-        t = truncate(Bm, delta, rmax, left_ortho, algorithm, batch, right_alloc)
+        t = truncate(Bm, delta, cut.rmax, cut.left_ortho, cut.algorithm, cut.batch, right_alloc)
     else:
         Bm = _hip.gemm(M, Q)                              # m x l: ... the fused column kernels
-        t = truncate(Bm, delta, rmax, left_ortho, algorithm, batch)
+        t = truncate(Bm, delta, cut.rmax, cut.left_ortho, cut.algorithm, cut.batch)
     if t.zero:
-        zl, zr = _zero_factors(M)
-        return Truncation(zl, None, zr, 1, zero=True, gtrace=gtr)
-    if not batch and t.rank < r:
+        return _zero_truncation(M, gtr)
+    if not cut.batch and t.rank < r:
         return None                                        # eps mode: the cap does not bind on the visible spectrum -- the full path decides
     if left_side:
         left = _hip.gemm(Q, t.left_scaled())
@@ -495,43 +495,100 @@ class Truncation:
         return _hip.scale_cols(self.left, self.colscale, _hip.SCALE_MUL)
 
 
-_ZF_PENDING = -(2 ** 31)   # (never a rank-rule result: those are >= 0)
+def _zero_truncation(M: torch.Tensor, gtrace=None) -> Truncation:
+    """The zero guard's result, round.py:137-145: rank-1 zero factors (kept on M's device/dtype)."""
+    Bt, m, n = M.shape
+    return Truncation(torch.zeros((Bt, m, 1), dtype=M.dtype, device=M.device), None,
+                      torch.zeros((Bt, 1, n), dtype=M.dtype, device=M.device), 1, zero=True, gtrace=gtrace)
 
 
-def _pinned_flag_wait(host: torch.Tensor):
-    """Callable that waits until the device has written the pinned host word ``host`` (initialised to ``_ZF_PENDING``; written by a
-    kernel of the current stream) and hands the tensor back.  Polls the word; after 2 s without a write it synchronises the
-    stream instead (the kernel's write is visible at the latest when the kernel has completed)."""
-    stream = torch.cuda.current_stream()
-
-    def wait() -> torch.Tensor:
-        import time
-
-        t0 = time.perf_counter()
-        while int(host.min()) == _ZF_PENDING:      # (every word: the device's stores become visible in no particular order)
-            if time.perf_counter() - t0 > 2.0:
-                stream.synchronize()
-                break
-        return host
-
-    return wait
+# ---- host words the device writes asynchronously
+_ZF_PENDING = -(2 ** 31)         # a polled word not yet written (never a rank-rule result: those are >= 0)
+_HOST_WORD_TIMEOUT_S = 2.0       # a polled word not written after this long: its stream is synchronised instead
+_HOST_WORD_TIGHT_POLLS = 32      # polls without a yield; after them time.sleep(0) follows each poll
 
 
-def _deferred_readback(x: torch.Tensor):
-    """Start an asynchronous copy of a small device tensor to pinned host memory on the current stream and return a
-    callable that waits for THAT copy (an event -- not a stream or device synchronisation) and hands back the host
-    tensor.  For control-flow scalars that are only needed once everything else has been enqueued: the host blocks,
-    the device never idles."""
-    host = torch.empty(x.shape, dtype=x.dtype, pin_memory=True)
-    host.copy_(x, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
+class _HostWord(NamedTuple):
+    host: torch.Tensor      # the words (pinned, or any host tensor)
+    stream: object          # the stream whose work writes them (anything with ``synchronize()``)
+    event: object = None    # recorded behind an asynchronous copy; None: a kernel stores the words directly and the host polls them
 
-    def wait() -> torch.Tensor:
-        ev.synchronize()
-        return host
 
-    return wait
+class _HostWords:
+    """Owner of the small host tensors that queued device work writes: the zero-guard flag and the eps-mode ranks ttr_round_tt
+    stores straight into pinned memory, and the deferred readbacks of control-flow scalars.  Such a block must not go back to the
+    pinned allocator with its write still pending (the allocator knows nothing of a kernel's store: the next small pinned
+    allocation would receive it), so ``with _HostWords() as words:`` spans the work that writes them: however the block is left,
+    every word not yet waited for is waited for -- or, if that wait is interrupted, its stream synchronised -- before it is released."""
+
+    def __init__(self):
+        self.open: List[_HostWord] = []   # issued and not yet waited for, in issue order
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        interrupted = None
+        for w in list(self.open):
+            try:
+                self._settle(w)
+            except BaseException as e:   # (a KeyboardInterrupt in the poll: the write must still land before the release)
+                w.stream.synchronize()
+                interrupted = interrupted or e
+            self._release(w)
+        if interrupted is not None and etype is None:
+            raise interrupted
+
+    def polled(self, host: torch.Tensor, stream) -> _HostWord:
+        """Issue ``host`` (int32, device-accessible; set to ``_ZF_PENDING`` here) for a kernel of ``stream`` to write every word of."""
+        self.open.append(_HostWord(host.fill_(_ZF_PENDING), stream))
+        return self.open[-1]
+
+    def pinned(self, n: int) -> _HostWord:
+        return self.polled(torch.empty(n, dtype=torch.int32, pin_memory=True), torch.cuda.current_stream())
+
+    def readback(self, x: torch.Tensor) -> _HostWord:
+        """Issue an asynchronous copy of a small device tensor to pinned memory on the current stream, waited for through an event
+        behind THAT copy (no stream or device synchronisation).  For control-flow scalars that are only needed once everything
+        else has been enqueued: the host blocks, the device never idles."""
+        host = torch.empty(x.shape, dtype=x.dtype, pin_memory=True)
+        host.copy_(x, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.open.append(_HostWord(host, torch.cuda.current_stream(), ev))
+        return self.open[-1]
+
+    def wait(self, w: _HostWord) -> torch.Tensor:
+        """The host tensor of ``w`` once the device has written it; a polled word the device never wrote is an error, not a value."""
+        written = self._settle(w)
+        self._release(w)
+        if not written:
+            raise RuntimeError("the library did not write a host word it was handed (still pending after its stream was synchronised): "
+                               f"libttround_hip.so does not implement TTR_ABI_VERSION {_hip.ABI_VERSION} as bound")
+        return w.host
+
+    def abandon(self, w: _HostWord) -> None:
+        """``w`` belongs to work that was given up part-way: it may never be written, and its value means nothing."""
+        w.stream.synchronize()
+        self._release(w)
+
+    def _settle(self, w: _HostWord) -> bool:
+        """Block until the device has written ``w``, or its stream has drained; False: the words are still pending then."""
+        if w.event is not None:
+            w.event.synchronize()
+            return True
+        polls, t0 = 0, time.perf_counter()
+        while int(w.host.min()) == _ZF_PENDING:   # (every word: the device's stores become visible in no particular order)
+            polls += 1
+            if polls > _HOST_WORD_TIGHT_POLLS:
+                if time.perf_counter() - t0 > _HOST_WORD_TIMEOUT_S:
+                    w.stream.synchronize()        # (the store is visible at the latest when the kernel has completed)
+                    return int(w.host.min()) != _ZF_PENDING
+                time.sleep(0)
+        return True
+
+    def _release(self, w: _HostWord) -> None:
+        self.open = [x for x in self.open if x is not w]
 
 
 # sigma_keep >= FLAT_SPECTRUM_THR * sigma_1: the second Gram pass of the 'svd' truncation is skipped for that item (batch
@@ -555,6 +612,20 @@ def _select_rank(info: torch.Tensor, batch: bool, rmax: Optional[int], k: int) -
 
 _INPLACE_ROTATE_BYTES = 1 << 32   # carries above 4 GiB are rotated in place ...
 _INPLACE_CHUNK_BYTES = 1 << 30    # ... through a 1 GiB buffer
+
+
+class _Cut(NamedTuple):
+    """The call as every path of ``truncate`` sees it: the caller's choices, then the scalars ``truncate`` derives from them."""
+    algorithm: str
+    left_ortho: bool
+    batch: bool
+    rmax: Optional[int]
+    want_trace: bool
+    k: int              # min(m, n)
+    use_delta: bool     # eps mode: the rank rule looks at delta^2
+    delta2: float
+    cap: int            # rmax as the rank rule takes it (INT32_MAX: none)
+    rcap: int           # ... and as a width: min(rmax, k), at least 1
 
 
 def truncate(
@@ -597,158 +668,158 @@ def truncate(
     orthonormal, ``right`` carries them.
     """
     Bt, m, n = M.shape
-    k = min(m, n)
     use_delta = not batch
     delta2 = float(delta) ** 2 if (delta is not None and use_delta) else 0.0
     cap = INT32_MAX if rmax is None else int(rmax)
+    cut = _Cut(algorithm, left_ortho, batch, rmax, want_trace, min(m, n), use_delta, delta2, cap, _rank_cap(rmax, min(m, n)))
     left_side = m <= n  # round.py:104-109; the 'svd' path is orientation-free
-    ref_clamp = algorithm == "eig"
-
     if left_side and _hip.sweep_fused_ok(M):
-        # Up to 64 rows (every bond of a train with TT ranks <= 64): the fused sweep kernels.  M is streamed three
-        # times ('eig': twice) and nothing of its size is written except the result: row Gram -> pass-1 eigenvectors V1
-        # -> Gram of the ROTATED rows (ttr_rotgram: the rotated matrix only exists 16 columns at a time in registers)
-        # -> Jacobi -> projection with U = V1 V2 formed in the kernel's prologue, which also emits left = U sigma.
-        V1 = None
-        st = _Stage()
-        G = gram if gram is not None else _hip.rowgram(M, rows32=rows32)
-        gtr = _gram_trace(G) if want_trace else None
-        if algorithm == "eig":
-            st.lap("Time (gram):")
-        if algorithm == "svd":
-            # r of the top-r launch: the rank cap in batch mode; in eps mode (any non-batch call) min(cap, 32) -- with `need_all`
-            # the top-r path then only serves the 32 x 32 zero-tail problems of packed bonds, whose whole spectrum that is
-            r_top = _rank_cap(rmax, k) if batch else min(_rank_cap(rmax, k), 32)
-            if ((rmax is not None or not batch) and EIGH_TOP_ENABLED and FLAT_SPECTRUM_THR > 0 and _hip.eigh_top_ok(k, r_top)):
-                # only the rmax largest eigenpairs matter when the kept spectrum is flat: multisection + twisted factorisations
-                # instead of the QL iteration over the whole spectrum, decided per item inside the launch (flat kept spectrum
-                # without close pairs; the others fall through to the QL phase).  Such items carry zeros beyond column / entry
-                # rmax, which nothing below looks at in batch mode.
-                # (the deferred eps-mode sweep, round 5: its rank rule needs EVERY sigma, so the top-r path only takes the items of
-                # which it computes every eigenpair -- the 32 x 32 zero-tail problems of a packed bond under a cap >= 32: 47 instead
-                # of ~100 us per bond of one 64^8 train; its flags are not the pass-through flags there)
-                V1, sig1, _, top_flat = _hip.eigh_top(G, r_top, FLAT_SPECTRUM_THR, need_all=not batch)
-                if not batch:
-                    top_flat = None
-            else:
-                V1, sig1, _ = _hip.eigh_trunc(G, _hip.EIG_RAW, False, 0.0, k, abs_floor=_hip.SOLVER_TRIDIAG)
-                top_flat = None
-            flat = None
-            if top_flat is not None and not use_delta:
-                # batch mode: the launch's flags are the pass-through flags already (1: top-r path; 2: declined there, but the
-                # full decomposition's kept sigma pass the same test) -- include/ttround_hip.h: ttr_eigh_top
-                flat = top_flat
-            elif FLAT_SPECTRUM_THR > 0:
-                # items whose KEPT singular values lie within a factor 8 of each other do not need the second pass (the first
-                # Gram matrix already carries them to a few eps; include/ttround_hip.h: ttr_spectrum_flat): their rotated
-                # Gram matrix is not formed and the pass-2 solver hands pass 1's result through.  Decided per item, on the
-                # device.  Batch mode: the rank does not depend on the small singular values.  eps mode: the rank rule is
-                # evaluated on pass 1's sigma and the item only qualifies when pass 2 provably selects the same rank (fp64
-                # trains: config C2; in fp32 the error margin of pass 1's tail energies exceeds a delta of 1e-4 ||T||).
-                flat = _hip.spectrum_flat(sig1, _rank_cap(rmax, k), FLAT_SPECTRUM_THR, use_delta, delta2, delta2_dev, rows32=rows32)
-                if top_flat is not None:
-                    # an item the top-r kernel decided on eigenvalues carries ONLY its r leading eigenpairs: it must pass through,
-                    # also when the same test on sigma = sqrt(lambda) rounds to the other side of the threshold ([B] int32 flags)
-                    flat = torch.maximum(flat, top_flat)
-            V, sig, info = _hip.eigh_trunc(_hip.rowgram(M, V1, skip=flat, rows32=rows32), _hip.EIG_RAW, use_delta, delta2, cap,
-                                           abs_floor=_hip.SOLVER_JACOBI_LIVE, delta2_dev=delta2_dev,
-                                           skip_items=flat, sigma_in=sig1 if flat is not None else None)
-        else:
-            V, sig, info = _hip.eigh_trunc(G, _hip.EIG_REF, use_delta, delta2, cap,
-                                           abs_floor=_hip.SOLVER_TRIDIAG, delta2_dev=delta2_dev)
-        st.lap("Time (SVD):" if algorithm == "svd" else "Time (symmetric EIG):")   # ('svd' here: both Gram passes + both solvers)
-        if delta2_dev is not None:  # rank on the device: factors at the cap, the columns beyond info[b] zeroed in place
-            r = _rank_cap(rmax, k)
-            right, left = _hip.project(M, V1, V, sig, r, scale_right=not left_ortho, rows32=rows32)
-            if algorithm == "svd" and not left_ortho:
-                _hip.orth_fixup(right, sig, r, k * torch.finfo(M.dtype).eps, rank_dev=info)  # (not the rows that are cut away)
-            _hip.mask_cols(left, info)
-            st.lap("Time (product):")
-            return Truncation(left, None, right, r, info=info, gtrace=gtr)
-        r = _select_rank(info, batch, rmax, k)
-        if r == 0:  # zero guard, round.py:137-145 (kept on M's device/dtype)
-            return Truncation(torch.zeros((Bt, m, 1), dtype=M.dtype, device=M.device), None,
-                              torch.zeros((Bt, 1, n), dtype=M.dtype, device=M.device), 1, zero=True, gtrace=gtr)
-        dst = right_alloc(r) if right_alloc is not None else None
-        right, left = _hip.project(M, V1, V, sig, r, scale_right=not left_ortho, out=dst, rows32=rows32)
-        if algorithm == "svd" and not left_ortho:
-            _hip.orth_fixup(right, sig, r, k * torch.finfo(M.dtype).eps)  # see below
-        st.lap("Time (product):")
-        return Truncation(left, None, right, r, info=info, gtrace=gtr)
-
+        return _truncate_rows64(M, cut, gram, right_alloc, delta2_dev, rows32)
     if not left_side and _hip.colsweep_fused_ok(M):
-        # Tall matrix with up to 64 columns (the first, largest steps of a dense right-to-left TT-SVD): the same fused
-        # kernels with the contraction over the rows.  The unfolding is read three times ('eig': twice) and only the
-        # carry (r / n of its size) is written -- no rotated copy of the input.
-        V1 = None
-        st = _Stage()
-        G0 = gram if gram is not None else _hip.colgram(M)
-        gtr = _gram_trace(G0) if want_trace else None
-        if algorithm == "eig":
-            st.lap("Time (gram):")
-        if algorithm == "svd":
-            V1, sig1, _ = _hip.eigh_trunc(G0, _hip.EIG_RAW, False, 0.0, k, abs_floor=_hip.SOLVER_TRIDIAG)
-            # (batch mode, or eps mode with the rank decision certified on pass 1's sigma: see the row sweep above)
-            flat = _hip.spectrum_flat(sig1, _rank_cap(rmax, k), FLAT_SPECTRUM_THR, use_delta, delta2) if FLAT_SPECTRUM_THR > 0 else None
-            V, sig, info = _hip.eigh_trunc(_hip.colgram(M, V1, skip=flat), _hip.EIG_RAW, use_delta, delta2, cap,
-                                           abs_floor=_hip.SOLVER_JACOBI_LIVE,
-                                           skip_items=flat, sigma_in=sig1 if flat is not None else None)  # (as the row sweep above)
-        else:
-            V, sig, info = _hip.eigh_trunc(G0, _hip.EIG_REF, use_delta, delta2, cap,
-                                           abs_floor=_hip.SOLVER_TRIDIAG)
-        st.lap("Time (SVD):" if algorithm == "svd" else "Time (symmetric EIG):")
-        r = _select_rank(info, batch, rmax, k)
-        if r == 0:
-            return Truncation(torch.zeros((Bt, m, 1), dtype=M.dtype, device=M.device), None,
-                              torch.zeros((Bt, 1, n), dtype=M.dtype, device=M.device), 1, zero=True, gtrace=gtr)
-        if consume and Bt == 1 and M.is_contiguous() and 2 * r <= n:
-            left, right = _colproject_inplace(M, V1, V, sig, r, left_ortho)
-        else:
-            left, right = _hip.colproject(M, V1, V, sig, r, left_ortho)
-        if algorithm == "svd" and left_ortho:
-            _hip.orth_fixup(left, sig, r, k * torch.finfo(M.dtype).eps, columns=True)
-        st.lap("Time (product):")
-        return Truncation(left, None, right, r, info=info, gtrace=gtr)
+        return _truncate_cols64(M, cut, gram, consume)
+    return _truncate_gemm(M, cut, gram, delta, right_alloc, scratch_ok)
 
+
+def _fused_eigs(G, rotgram, cut, st, top=None, delta2_dev=None, rows32=None):
+    """The solver step of both fused sweeps, from the first Gram matrix ``G`` to the rank rule: (V1, V, sigma, info).  'svd': pass-1
+    eigenvectors V1 -> per-item flat-spectrum flags -> ``rotgram(V1, flat)``, the Gram matrix of the ROTATED rows / columns ->
+    Jacobi.  'eig': one QL solve of G, V1 None.  Row sweep only: ``top``, its top-r solver's pass 1 (V1, sigma1, flags or None)."""
+    algorithm, left_ortho, batch, rmax, want_trace, k, use_delta, delta2, cap, rcap = cut
+    if algorithm == "eig":
+        st.lap("Time (gram):")
+        V, sig, info = _hip.eigh_trunc(G, _hip.EIG_REF, use_delta, delta2, cap,
+                                       abs_floor=_hip.SOLVER_TRIDIAG, delta2_dev=delta2_dev)
+        st.lap("Time (symmetric EIG):")
+        return None, V, sig, info
+    if top is not None:
+        V1, sig1, flat = top
+    else:
+        V1, sig1, _ = _hip.eigh_trunc(G, _hip.EIG_RAW, False, 0.0, k, abs_floor=_hip.SOLVER_TRIDIAG)
+        flat = None
+    if flat is None and FLAT_SPECTRUM_THR > 0:
+        # items whose KEPT singular values lie within a factor 8 of each other do not need the second pass (the first
+        # Gram matrix already carries them to a few eps; include/ttround_hip.h: ttr_spectrum_flat): their rotated
+        # Gram matrix is not formed and the pass-2 solver hands pass 1's result through.  Decided per item, on the
+        # device.  Batch mode: the rank does not depend on the small singular values.  eps mode: the rank rule is
+        # evaluated on pass 1's sigma and the item only qualifies when pass 2 provably selects the same rank (fp64
+        # trains: config C2; in fp32 the error margin of pass 1's tail energies exceeds a delta of 1e-4 ||T||).
+        flat = _hip.spectrum_flat(sig1, rcap, FLAT_SPECTRUM_THR, use_delta, delta2, delta2_dev, rows32=rows32)
+    V, sig, info = _hip.eigh_trunc(rotgram(V1, flat), _hip.EIG_RAW, use_delta, delta2, cap,
+                                   abs_floor=_hip.SOLVER_JACOBI_LIVE, delta2_dev=delta2_dev,
+                                   skip_items=flat, sigma_in=sig1 if flat is not None else None)
+    st.lap("Time (SVD):")   # (both Gram passes + both solvers)
+    return V1, V, sig, info
+
+
+def _truncate_rows64(M, cut, gram, right_alloc, delta2_dev, rows32) -> Truncation:
+    """Up to 64 rows (every bond of a train with TT ranks <= 64): the fused sweep kernels.  M is streamed three times ('eig':
+    twice) and nothing of its size is written except the result: row Gram -> pass-1 eigenvectors V1 -> Gram of the ROTATED rows
+    (ttr_rotgram: the rotated matrix only exists 16 columns at a time in registers) -> Jacobi -> projection with U = V1 V2
+    formed in the kernel's prologue, which also emits left = U sigma."""
+    algorithm, left_ortho, batch, rmax, want_trace, k, use_delta, delta2, cap, rcap = cut
+    st = _Stage()
+    G = gram if gram is not None else _hip.rowgram(M, rows32=rows32)
+    gtr = _gram_trace(G) if want_trace else None
+    top = None
+    if algorithm == "svd":
+        # r of the top-r launch: the rank cap in batch mode; in eps mode (any non-batch call) min(cap, 32) -- with `need_all`
+        # the top-r path then only serves the 32 x 32 zero-tail problems of packed bonds, whose whole spectrum that is
+        r_top = rcap if batch else min(rcap, 32)
+        if (rmax is not None or not batch) and EIGH_TOP_ENABLED and FLAT_SPECTRUM_THR > 0 and _hip.eigh_top_ok(k, r_top):
+            # only the rmax largest eigenpairs matter when the kept spectrum is flat: multisection + twisted factorisations
+            # instead of the QL iteration over the whole spectrum, decided per item inside the launch (flat kept spectrum
+            # without close pairs; the others fall through to the QL phase).  Such items carry zeros beyond column / entry
+            # rmax, which nothing below looks at in batch mode.
+            # (the deferred eps-mode sweep, round 5: its rank rule needs EVERY sigma, so the top-r path only takes the items of
+            # which it computes every eigenpair -- the 32 x 32 zero-tail problems of a packed bond under a cap >= 32: 47 instead
+            # of ~100 us per bond of one 64^8 train; its flags are not the pass-through flags there)
+            V1, sig1, _, top_flat = _hip.eigh_top(G, r_top, FLAT_SPECTRUM_THR, need_all=not batch)
+            # batch mode: the launch's flags are the pass-through flags already (1: top-r path; 2: declined there, but the
+            # full decomposition's kept sigma pass the same test) -- include/ttround_hip.h: ttr_eigh_top
+            top = (V1, sig1, top_flat if batch else None)
+    V1, V, sig, info = _fused_eigs(G, lambda v1, flat: _hip.rowgram(M, v1, skip=flat, rows32=rows32), cut, st, top, delta2_dev, rows32)
+    # ``delta2_dev``: the rank stays on the device -- factors at the cap, the columns beyond info[b] zeroed in place
+    deferred = delta2_dev is not None
+    r = rcap if deferred else _select_rank(info, batch, rmax, k)
+    if r == 0:
+        return _zero_truncation(M, gtr)
+    dst = right_alloc(r) if right_alloc is not None else None
+    right, left = _hip.project(M, V1, V, sig, r, scale_right=not left_ortho, out=dst, rows32=rows32)
+    if algorithm == "svd" and not left_ortho:
+        # (see ``_truncate_gemm``; deferred: not the rows that are cut away)
+        _hip.orth_fixup(right, sig, r, k * torch.finfo(M.dtype).eps, rank_dev=info if deferred else None)
+    if deferred:
+        _hip.mask_cols(left, info)
+    st.lap("Time (product):")
+    return Truncation(left, None, right, r, info=info, gtrace=gtr)
+
+
+def _truncate_cols64(M, cut, gram, consume) -> Truncation:
+    """Tall matrix with up to 64 columns (the first, largest steps of a dense right-to-left TT-SVD): the same fused kernels with
+    the contraction over the rows.  The unfolding is read three times ('eig': twice) and only the carry (r / n of its size) is
+    written -- no rotated copy of the input."""
+    algorithm, left_ortho, batch, rmax, want_trace, k, use_delta, delta2, cap, rcap = cut
+    Bt, m, n = M.shape
+    st = _Stage()
+    G0 = gram if gram is not None else _hip.colgram(M)
+    gtr = _gram_trace(G0) if want_trace else None
+    V1, V, sig, info = _fused_eigs(G0, lambda v1, flat: _hip.colgram(M, v1, skip=flat), cut, st)
+    r = _select_rank(info, batch, rmax, k)
+    if r == 0:
+        return _zero_truncation(M, gtr)
+    if consume and Bt == 1 and M.is_contiguous() and 2 * r <= n:
+        left, right = _colproject_inplace(M, V1, V, sig, r, left_ortho)
+    else:
+        left, right = _hip.colproject(M, V1, V, sig, r, left_ortho)
+    if algorithm == "svd" and left_ortho:
+        _hip.orth_fixup(left, sig, r, k * torch.finfo(M.dtype).eps, columns=True)
+    st.lap("Time (product):")
+    return Truncation(left, None, right, r, info=info, gtrace=gtr)
+
+
+def _truncate_gemm(M, cut, gram, delta, right_alloc, scratch_ok) -> Truncation:
+    """Everything else: Gram matrices, rotations and projections as GEMMs, the eigenproblems through ``_eigh_any``.
+    ``delta``: as ``truncate`` got it (the range finder calls ``truncate`` again)."""
+    Bt, m, n = M.shape
+    algorithm, left_ortho, batch, rmax, want_trace, k, use_delta, delta2, cap, rcap = cut
+    left_side = m <= n
     one_pass = None
     st = _Stage()
+    G = gram if gram is not None else (_hip.gemm(M, M, transB=True) if left_side else _hip.gemm(M, M, transA=True))
+    gtr = _gram_trace(G) if want_trace else None
     if algorithm == "svd":
         # ---- pass 1: rotate into (nearly) orthogonal rows / columns
-        G = gram if gram is not None else (_hip.gemm(M, M, transB=True) if left_side else _hip.gemm(M, M, transA=True))
-        gtr = _gram_trace(G) if want_trace else None
         # Batch mode: pass 1 is run to full accuracy and, when EVERY item's kept singular values lie within 1 / FLAT_SPECTRUM_THR
-        # of each other, it is the answer (see the fused path above) -- the rotation GEMM, the second Gram matrix and the
+        # of each other, it is the answer (see ``_fused_eigs``) -- the rotation GEMM, the second Gram matrix and the
         # second eigenproblem, i.e. two of the three passes over M, are not enqueued at all.  The decision concerns launches
         # on the host, hence one flag readback per such bond (dense batches: BASELINE config C3; the bonds of a TT-to-TT
         # rounding have <= 64 rows and decide per item on the device).  Otherwise pass 1 is a pre-rotation.
         try_flat = batch and FLAT_SPECTRUM_THR > 0
         if (batch or rmax is not None) and min(m, n) > 64:
             # concentrated spectra (low rank + noise, decaying): certified range finder + the fused small truncation
-            sub = _subspace_truncate(M, G, _rank_cap(rmax, k), delta, rmax, left_ortho, algorithm, batch, right_alloc, gtr)
+            sub = _subspace_truncate(M, G, cut, delta, right_alloc, gtr)
             if sub is not None:
-                _trace("subspace", m, n, _rank_cap(rmax, k))
+                _trace("subspace", m, n, rcap)
                 return sub
         if FLAT_SPECTRUM_THR > 0 and (batch or rmax is not None):
             # (eps mode with a rank cap -- a single dense tensor to given ranks, BASELINE config C1: only when the cap provably binds)
-            one_pass = _topk_one_pass(G, _rank_cap(rmax, k), use_delta, delta2)
+            one_pass = _topk_one_pass(G, rcap, use_delta, delta2)
         if one_pass is not None:
-            V1, Mw = None, M
-            _trace("topk_one_pass", m, n, _rank_cap(rmax, k))
+            _trace("topk_one_pass", m, n, rcap)
         else:
             V1, sig1, info1 = _eigh_any(G, _hip.EIG_RAW, False, 0.0, cap if try_flat else k, _hip.SOLVER_TRIDIAG,
                                         prerotation=not try_flat)
+            if try_flat and int(_hip.spectrum_flat(sig1, rcap, FLAT_SPECTRUM_THR).amin().item()) == 1:
+                one_pass = (V1, sig1, info1)
+                _trace("full_one_pass", m, n, rcap)
+            else:
+                _trace("full_two_pass", m, n, rcap)
         if one_pass is not None:
-            pass
-        elif try_flat and int(_hip.spectrum_flat(sig1, _rank_cap(rmax, k), FLAT_SPECTRUM_THR).amin().item()) == 1:
-            one_pass = (V1, sig1, info1)
             V1, Mw = None, M
-            _trace("full_one_pass", m, n, _rank_cap(rmax, k))
         elif left_side:
-            _trace("full_two_pass", m, n, _rank_cap(rmax, k))
             Mw = _hip.gemm(V1, M, transA=True)           # V1^T M
             G = _hip.gemm(Mw, Mw, transB=True)
         else:
-            _trace("full_two_pass", m, n, _rank_cap(rmax, k))
             if scratch_ok and M.is_contiguous() and M.numel() * M.element_size() > _INPLACE_ROTATE_BYTES:
                 # config-scale carries (C1 class: tens of GiB): every row of M V1 depends on the same row of M only, so
                 # the rotation runs chunk by chunk into a bounded buffer that is copied back over its source rows
@@ -763,8 +834,6 @@ def truncate(
     else:
         V1 = None
         Mw = M
-        G = gram if gram is not None else (_hip.gemm(M, M, transB=True) if left_side else _hip.gemm(M, M, transA=True))
-        gtr = _gram_trace(G) if want_trace else None
 
     # 'eig' (and pass 1 above): absolute accuracy is all a plain Gram matrix carries -> tridiagonal QL solver;
     # pass 2 of 'svd': graded, accurately formed Gram matrix -> Jacobi (relative accuracy of the small sigmas)
@@ -772,7 +841,7 @@ def truncate(
     if one_pass is not None:
         V, sig, info = one_pass
     else:
-        V, sig, info = _eigh_any(G, _hip.EIG_REF if ref_clamp else _hip.EIG_RAW, use_delta, delta2, cap,
+        V, sig, info = _eigh_any(G, _hip.EIG_REF if algorithm == "eig" else _hip.EIG_RAW, use_delta, delta2, cap,
                                  _hip.SOLVER_TRIDIAG if algorithm == "eig" else _hip.SOLVER_JACOBI_LIVE)
     # 'svd': kept directions whose sigma lies below the resolution of the input (k eps sigma_max) carry rounding
     # noise only; LAPACK's V is orthonormal there too (round.py:96), so they get an orthonormal completion
@@ -780,10 +849,8 @@ def truncate(
     dead_rel = k * torch.finfo(M.dtype).eps if algorithm == "svd" else None
     st.lap("Time (SVD):" if algorithm == "svd" else "Time (gram + symmetric EIG):")
     r = _select_rank(info, batch, rmax, k)
-    if r == 0:  # zero guard, round.py:137-145 (kept on M's device/dtype)
-        z_l = torch.zeros((Bt, m, 1), dtype=M.dtype, device=M.device)
-        z_r = torch.zeros((Bt, 1, n), dtype=M.dtype, device=M.device)
-        return Truncation(z_l, None, z_r, 1, zero=True, gtrace=gtr)
+    if r == 0:
+        return _zero_truncation(M, gtr)
     Vr = V[:, :, :r]
 
     if left_side:
@@ -866,27 +933,24 @@ def _range_guard_from_norms(nr: torch.Tensor):
     return e
 
 
-def _zero_factors(M3):
-    Bt, m, n = M3.shape
-    return (torch.zeros((Bt, m, 1), dtype=M3.dtype, device=M3.device), torch.zeros((Bt, 1, n), dtype=M3.dtype, device=M3.device))
-
-
 def _truncated_svd_batch(M3, rmax, left_ortho, algorithm):
     """Batch mode of ``truncated_svd``: the rank is not data dependent (round.py:149-150), so the kernels are enqueued
     optimistically and the two data-dependent exceptions -- an fp32 item outside the 2^+-40 exponent window (the range
     guard: redo with scaled inputs) and an all-zero batch (round.py:138-141: rank-1 zeros) -- are decided from flags read
     back ONCE, after everything has been enqueued (no host wait in front of any kernel)."""
     Bt = M3.shape[0]
-    range_flag = None
-    if M3.dtype == torch.float32:
-        _, e = _hip.pow2_normalize(_hip.norm(M3.reshape(Bt, -1)).reshape(-1, 1), exponent_only=True)
-        range_flag = _deferred_readback(e.abs().amax())
-    t = truncate(M3, None, rmax, left_ortho, algorithm, True)
-    zero_flag = _deferred_readback(t.info.amax()) if t.info is not None else None
-    if range_flag is not None and int(range_flag().item()) >= 40:
-        return None  # (rare) the caller takes the scaled path
-    if zero_flag is not None and int(zero_flag().item()) == 0:
-        return _zero_factors(M3)
+    with _HostWords() as words:
+        range_flag = None
+        if M3.dtype == torch.float32:
+            _, e = _hip.pow2_normalize(_hip.norm(M3.reshape(Bt, -1)).reshape(-1, 1), exponent_only=True)
+            range_flag = words.readback(e.abs().amax())
+        t = truncate(M3, None, rmax, left_ortho, algorithm, True)
+        zero_flag = words.readback(t.info.amax()) if t.info is not None else None
+        if range_flag is not None and int(words.wait(range_flag).item()) >= 40:
+            return None  # (rare) the caller takes the scaled path
+        if zero_flag is not None and int(words.wait(zero_flag).item()) == 0:
+            t = _zero_truncation(M3)
+            return t.left, t.right
     left = t.left_scaled()
     return (left if left.is_contiguous() else left.contiguous()), t.right
 
@@ -908,7 +972,8 @@ def truncated_svd(M3, delta, eps, rmax, left_ortho, algorithm, batch):
         delta = 0.0
     t = truncate(M3, delta, rmax, left_ortho, algorithm, batch)
     if batch and t.info is not None and int(t.info.amax().item()) == 0:  # round.py:138-141 (scaled path: exact zeros only)
-        return _zero_factors(M3)
+        t = _zero_truncation(M3)
+        return t.left, t.right
     left = t.left_scaled()
     if not left.is_contiguous():
         left = left.contiguous()
@@ -1168,43 +1233,49 @@ def round_tt(
     # of a batch are otherwise not data dependent, so the sweep is enqueued for them without waiting; the per-item flags
     # the eigensolver epilogue leaves behind (info == 0) are reduced on the device, copied to pinned host memory and only
     # looked at after the last kernel of the sweep has been enqueued.
-    zflags: Optional[list] = [] if batch else None
-    shapes = [tuple(x.shape[1:]) for x in c]
+    # (``words`` owns those host words -- and the ranks an eps-mode sweep leaves in pinned memory -- until they are written)
+    shapes, dt, dev = [tuple(x.shape[1:]) for x in c], c[0].dtype, c[0].device
+    with _HostWords() as words:
+        if nchunk == 1:
+            out = _round_tt_sweep(c, eps, rmax, algorithm, batch, None, 0, words)
+        else:
+            main = torch.cuda.current_stream(dev)
+            streams = _side_streams(dev, nchunk)
+            q, rem = divmod(Bt, nchunk)
+            bounds = [(ci * q + min(ci, rem), (ci + 1) * q + min(ci + 1, rem)) for ci in range(nchunk)]
+            tails, out_r = _rounded_tails(shapes, rmax)
+            arena = _OutArena(Bt, bounds, main, tails, c[0])
+            try:
+                for ci, st in enumerate(streams):
+                    st.wait_stream(main)
+                    with torch.cuda.stream(st):
+                        lo, hi = bounds[ci]
+                        _round_tt_sweep([x[lo:hi] for x in c], eps, rmax, algorithm, batch, arena, ci, words)
+            finally:
+                for st in streams:   # (also when a chunk raised: the arena goes back to the main stream's allocator)
+                    main.wait_stream(st)
+            out = [arena.full[mu].view(Bt, out_r[mu], shapes[mu][1], out_r[mu + 1]) for mu in range(N)]
+        # (every flag is waited for, also when the first one already decides; non-batch calls: no flags at all)
+        flags = [int(words.wait(w).reshape(-1)[0].item()) for w in words.open]
+    if flags and all(v == 0 for v in flags):
+        return _zero_train(shapes, Bt, dt, dev)
+    return out
 
-    def all_zero_batch() -> bool:
-        # (every flag is waited for, also when the first one already decides: a pinned word must not be handed back to the
-        # allocator before the device has written it)
-        vals = [int(w().reshape(-1)[0].item()) for w in (zflags or ())]   # (non-batch calls: no flags at all)
-        return bool(vals) and all(v == 0 for v in vals)
 
-    def zero_train():
-        return [torch.zeros((Bt, shapes[0][0] if mu == 0 else 1, shapes[mu][1], shapes[N - 1][2] if mu == N - 1 else 1),
-                            dtype=c[0].dtype, device=c[0].device) for mu in range(N)]
+def _zero_train(shapes, Bt: int, dtype, device) -> List[torch.Tensor]:
+    """The zero guard at every bond (round.py:137-145): rank-1 zero cores between the boundary ranks of ``shapes`` [(r0, I, r1), ...]."""
+    N = len(shapes)
+    return [torch.zeros((Bt, shapes[0][0] if mu == 0 else 1, shapes[mu][1], shapes[N - 1][2] if mu == N - 1 else 1),
+                        dtype=dtype, device=device) for mu in range(N)]
 
-    if nchunk == 1:
-        out = _round_tt_sweep(c, eps, rmax, algorithm, batch, None, 0, zflags)
-        return zero_train() if all_zero_batch() else out
-    dev = c[0].device
-    main = torch.cuda.current_stream(dev)
-    streams = _side_streams(dev, nchunk)
-    q, rem = divmod(Bt, nchunk)
-    bounds, lo = [], 0
-    for ci in range(nchunk):
-        hi = lo + q + (1 if ci < rem else 0)
-        bounds.append((lo, hi))
-        lo = hi
-    tails, out_r = _rounded_tails(shapes, rmax)
-    arena = _OutArena(Bt, bounds, main, tails, c[0])
-    for ci, st in enumerate(streams):
-        st.wait_stream(main)
-        with torch.cuda.stream(st):
-            lo, hi = bounds[ci]
-            _round_tt_sweep([x[lo:hi] for x in c], eps, rmax, algorithm, batch, arena, ci, zflags)
-    for st in streams:
-        main.wait_stream(st)
-    if all_zero_batch():
-        return zero_train()
-    return [arena.full[mu].view(Bt, out_r[mu], shapes[mu][1], out_r[mu + 1]) for mu in range(N)]
+
+def _cut_to_ranks(c, ranks, shapes) -> List[torch.Tensor]:
+    """End of a deferred eps-mode sweep on one train: the cores ``c`` -- computed at their caps, zero beyond the selected ``ranks``
+    (ranks[mu - 1]: bond mu) -- cut to size (layout copies), or the zero train when the carry was zero from the first bond on."""
+    if min(ranks) == 0:
+        return _zero_train(shapes, 1, c[0].dtype, c[0].device)
+    bond = [shapes[0][0]] + ranks + [shapes[-1][2]]
+    return [x[:, :bond[mu], :, :bond[mu + 1]].contiguous() for mu, x in enumerate(c)]
 
 
 # The whole sweep behind ONE library call (ttr_round_tt, csrc/ttr_roundtt.hip): same kernels, same order, bit-identical results --
@@ -1218,7 +1289,7 @@ FUSE_QR_NORM = os.environ.get("TTR_FUSE_QR_NORM", "1") != "0"
 SWEEP_C_CALLS = 0   # (tests: how many sweeps went through ttr_round_tt)
 
 
-def _round_tt_sweep_c(c, eps, rmax, algorithm, batch, arena, chunk, zflags) -> Optional[List[torch.Tensor]]:
+def _round_tt_sweep_c(c, eps, rmax, algorithm, batch, arena, chunk, words) -> Optional[List[torch.Tensor]]:
     """``_round_tt_sweep`` through ttr_round_tt, or None when the train lies outside that entry's envelope (TT ranks above 64,
     cores outside the fused push, bonds with more rows than columns, fused sums, the eps-mode cases the Python loop reads back
     bond by bond)."""
@@ -1232,18 +1303,8 @@ def _round_tt_sweep_c(c, eps, rmax, algorithm, batch, arena, chunk, zflags) -> O
     shapes = [tuple(x.shape[1:]) for x in c]
     eps_mode = not batch
     rcap = [_hip.RANK_NONE if r is None else max(1, min(int(r), _hip.RANK_NONE)) for r in rmax]
-    if eps_mode:
-        # the reference's non-batch rule with the ranks kept on the device (see ``_eps_deferred_ok``: same policy)
-        mode = os.environ.get("TTR_EPS_DEFERRED", "auto")
-        if mode == "0" or Bt != 1:
-            return None
-        k, elems = shapes[0][0], 0
-        for mu in range(N - 1):
-            elems += k * shapes[mu][1] * shapes[mu][2]
-            k = min(k * shapes[mu][1], shapes[mu][2])
-        elems += k * shapes[N - 1][1] * shapes[N - 1][2]
-        if mode != "1" and (elems > _EPS_DEFERRED_MAX_ELEMS or any(r is None for r in rmax)):
-            return None
+    if eps_mode and not _eps_deferred_policy(shapes, Bt, rmax):
+        return None   # (the reference's non-batch rule runs here only with the ranks kept on the device)
     wsb = _hip.round_tt_plan(c[0].dtype, shapes, rcap, Bt, eps_mode)
     if wsb < 0:
         return None
@@ -1256,52 +1317,37 @@ def _round_tt_sweep_c(c, eps, rmax, algorithm, batch, arena, chunk, zflags) -> O
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
     ranks_dev = torch.empty(N - 1, dtype=torch.int32, device=dev) if eps_mode else None
     # the zero-guard flag (round.py:138-141 for the whole batch): the sweep's reduction kernel writes it STRAIGHT into pinned host
-    # memory right after the first truncation (ttr_round_tt accepts any device-accessible address), the host polls the word.  As a
-    # device word copied back after the call (rounds 5: a copy + event at the END of the stream) the caller waited for the whole
-    # sweep before it could return -- one 64^8 train: 1.27 ms per call where the host loop, whose flag travels early, took 1.18.
-    zf = None
-    if zflags is not None and not eps_mode:
-        zf = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        zf[0] = _ZF_PENDING
-    elif eps_mode and N - 1 <= 64:
-        # (eps mode: the same word pattern for the selected ranks -- an early copy of ranks_dev in pinned host memory)
-        zf = torch.full((N - 1,), _ZF_PENDING, dtype=torch.int32).pin_memory()
+    # memory right after the first truncation (ttr_round_tt accepts any device-accessible address) and the host polls the word: a
+    # copy + event at the END of the stream would make the caller wait for the whole sweep.  eps mode: the same pattern for the
+    # selected ranks, an early copy of ranks_dev.
+    zf = words.pinned(1 if batch else N - 1) if (batch or N - 1 <= 64) else None
     use_top = EIGH_TOP_ENABLED and FLAT_SPECTRUM_THR > 0
     try:
         _hip.round_tt_sweep([x.contiguous() for x in c], rcap, algorithm, eps_mode, eps if eps is not None else 0.0,
-                            max(FLAT_SPECTRUM_THR, 0.0), use_top, outs, ranks_dev, zf, ws)
+                            max(FLAT_SPECTRUM_THR, 0.0), use_top, outs, ranks_dev, zf.host if zf is not None else None, ws)
     except NotImplementedError:
         # a per-kernel limit the planner does not mirror (TTR_E_UNSUPPORTED from inside the sweep): ttr_round_tt never writes its
         # inputs, so the loop over the per-kernel entries -- which asks every kernel's own predicate -- starts from the same state
+        # (the part of the sweep that was enqueued may or may not write the word: nothing is read from it)
+        if zf is not None:
+            words.abandon(zf)
         return None
     SWEEP_C_CALLS += 1
-    if zf is not None and not eps_mode:
-        zflags.append(_pinned_flag_wait(zf))
     out = [outs[mu].view(Bt, out_r[mu], shapes[mu][1], out_r[mu + 1]) for mu in range(N)]
     if eps_mode:
-        # the ONE host synchronisation of the sweep: the selected ranks; the cores -- computed at their caps, zero beyond the
-        # selected ranks -- are cut to size (layout copies)
-        # (polled from the pinned copy: available before the sweep's last kernels have run)
-        if zf is not None:
-            _pinned_flag_wait(zf)()
-            ranks = zf.tolist()                         # ranks[mu - 1] = rank of bond mu
-        else:
-            ranks = ranks_dev.tolist()
-        if min(ranks) == 0:  # zero guard (round.py:137-145): the carry was zero from the first bond on
-            return [torch.zeros((1, shapes[0][0] if mu == 0 else 1, shapes[mu][1], shapes[N - 1][2] if mu == N - 1 else 1),
-                                dtype=dt, device=dev) for mu in range(N)]
-        bond = [shapes[0][0]] + ranks + [shapes[N - 1][2]]
-        out = [x[:, :bond[mu], :, :bond[mu + 1]].contiguous() for mu, x in enumerate(out)]
+        # the ONE host synchronisation of the sweep: the selected ranks (polled from the pinned copy: available before the sweep's
+        # last kernels have run)
+        return _cut_to_ranks(out, (words.wait(zf) if zf is not None else ranks_dev).tolist(), shapes)
     return out
 
 
-def _round_tt_sweep(c, eps, rmax, algorithm, batch, arena, chunk, zflags=None) -> List[torch.Tensor]:
+def _round_tt_sweep(c, eps, rmax, algorithm, batch, arena, chunk, words) -> List[torch.Tensor]:
     """The two sweeps on one (sub-)batch; with an ``arena`` the resulting cores are written into its slices.
-    ``zflags``: list that receives the deferred readback of "largest rank-rule result of the first truncation" (0 = every
-    item of this sub-batch hit the zero guard); see ``round_tt``."""
+    ``words`` (``_HostWords`` of the call): in batch mode it is left holding the host word "largest rank-rule result of the first
+    truncation" (0 = every item of this sub-batch hit the zero guard); see ``round_tt``."""
     N = len(c)
     if SWEEP_C_ENABLED and not VERBOSE and not _FUSE_APPLY_GRAM:
-        done = _round_tt_sweep_c(c, eps, rmax, algorithm, batch, arena, chunk, zflags)
+        done = _round_tt_sweep_c(c, eps, rmax, algorithm, batch, arena, chunk, words)
         if done is not None:
             return done
     facs = []
@@ -1311,29 +1357,22 @@ def _round_tt_sweep(c, eps, rmax, algorithm, batch, arena, chunk, zflags=None) -
     for mu in range(N - 1):  # L2R: tensor.py:1905-1906 (Q implicit, push fused into the next QR)
         Bt, r0, I, r1 = c[mu].shape
         rows_k = r0 if Rprev is None else Rprev.shape[1]
-        if isinstance(c[mu], SumCore):
-            if Rprev is not None and _hip.pushed_supported(Rprev.shape[1], r0, I, r1, c[mu].dtype):
-                f = _hip.qr_factor_pushed_sum(Rprev, c[mu].a, c[mu].b)  # blockdiag(a, b) is never materialised
-                facs.append((f, rows_k, I))
-                Rprev = f.R
-                if Rprev.dtype == torch.float32:
-                    if expo is None:
-                        expo = torch.zeros(Bt, dtype=torch.int32, device=Rprev.device)
-                    Rprev, _ = _hip.pow2_normalize(Rprev, expo_acc=expo)
-                c[mu] = None
-                continue
-            c[mu] = c[mu].dense()  # ranks above the fused kernel's 64 columns: the padded core after all
         # fp32: ||R_mu|| is the norm of the partially contracted tensor and grows like (I r)^(mu/2): the squared
         # column norms / Gram entries of a high-order train overflow fp32 (LAPACK rescales internally).  Every R
         # is therefore brought back to O(1) by an exact power of two per batch item -- by the factor kernel itself
-        # (``expo_acc``: ttr_qr_factor_expo; rounds 1 - 4 and the explicit-Q path: one ttr_pow2_normalize launch) -- ; the
-        # exponents are summed on the device and returned to core 0 at the end, so the result is bit-identical whenever
+        # (``expo_acc``: ttr_qr_factor_expo; rounds 1 - 4, the explicit-Q path and the fused sum: one ttr_pow2_normalize launch)
+        # -- ; the exponents are summed on the device and returned to core 0 at the end, so the result is bit-identical whenever
         # nothing overflowed.
         f32 = c[mu].dtype == torch.float32
         if f32 and expo is None:
             expo = torch.zeros(Bt, dtype=torch.int32, device=c[mu].device)
-        ex = expo if (f32 and FUSE_QR_NORM) else None
-        if r1 > _hip.max_qr_cols(c[mu].dtype):
+        ex = expo if (f32 and FUSE_QR_NORM) else None   # (stays set only where the factor kernel normalises R itself)
+        if isinstance(c[mu], SumCore) and not (Rprev is not None and _hip.pushed_supported(Rprev.shape[1], r0, I, r1, c[mu].dtype)):
+            c[mu] = c[mu].dense()  # ranks above the fused kernel's 64 columns: the padded core after all
+        if isinstance(c[mu], SumCore):
+            f = _hip.qr_factor_pushed_sum(Rprev, c[mu].a, c[mu].b)  # blockdiag(a, b) is never materialised
+            ex = None
+        elif r1 > _hip.max_qr_cols(c[mu].dtype):
             # more columns than a TSQR panel holds (TT rank > 64): explicit Q from the blocked QR
             A = c[mu] if Rprev is None else _hip.gemm(Rprev, c[mu].reshape(Bt, r0, I * r1))
             f = _ExplicitQ(*qr(A.reshape(Bt, rows_k * I, r1)))
@@ -1392,10 +1431,9 @@ def _round_tt_sweep(c, eps, rmax, algorithm, batch, arena, chunk, zflags=None) -
             M4 = M4.reshape(f.batch, r0, I, left.shape[2])
         Bt, R, I, rn = M4.shape
         # rows kk >= 32 of the carry are exactly zero for the items whose QR of this bond packed its rows
-        if mu < N - 1:
-            r32 = getattr(facs[mu][0], "rows32", None) if (R == 64 and I * rn >= 64) else None
-        else:
-            r32 = r32_last if (R == 64 and I * rn >= 64) else None
+        r32 = None
+        if R == 64 and I * rn >= 64:
+            r32 = r32_last if mu == N - 1 else getattr(facs[mu][0], "rows32", None)
         alloc = None
         if arena is not None:
             def alloc(r, mu=mu, n=I * rn):
@@ -1404,8 +1442,8 @@ def _round_tt_sweep(c, eps, rmax, algorithm, batch, arena, chunk, zflags=None) -
                      rows32=r32)
         if d2dev is not None:
             infos.append(t.info)
-        if zflags is not None and mu == N - 1 and t.info is not None:
-            zflags.append(_deferred_readback(t.info.amax()))  # ([B] int32 -> one scalar: control flow only)
+        if batch and mu == N - 1 and t.info is not None:
+            words.readback(t.info.amax())  # ([B] int32 -> one scalar: control flow only)
         right = t.right
         if arena is not None:
             dst = alloc(t.rank)
@@ -1422,45 +1460,55 @@ def _round_tt_sweep(c, eps, rmax, algorithm, batch, arena, chunk, zflags=None) -
         dst = arena.slice(0, chunk, (r0 * I, left.shape[2]))
     c[0] = _apply_q(f, left, dst).reshape(f.batch, r0, I, left.shape[2])
     if d2dev is not None:
-        # the ONE host synchronisation of the sweep: the selected ranks (bond N-1 first), then the cores -- computed at their
-        # caps, zero beyond the selected ranks -- are cut to size (layout copies)
-        ranks = torch.cat(infos).tolist()[::-1]          # ranks[mu - 1] = rank of bond mu
-        if min(ranks) == 0:  # zero guard (round.py:137-145): the carry was zero from the first bond on
-            return [torch.zeros((1, c[0].shape[1] if mu == 0 else 1, c[mu].shape[2], c[N - 1].shape[3] if mu == N - 1 else 1),
-                                dtype=c[0].dtype, device=c[0].device) for mu in range(N)]
-        bond = [c[0].shape[1]] + ranks + [c[N - 1].shape[3]]
-        c = [x[:, :bond[mu], :, :bond[mu + 1]].contiguous() for mu, x in enumerate(c)]
+        # the ONE host synchronisation of the sweep: the selected ranks (bond N-1 first)
+        return _cut_to_ranks(c, torch.cat(infos).tolist()[::-1], [tuple(x.shape[1:]) for x in c])
     return c
 
 
 _EPS_DEFERRED_MAX_ELEMS = 1 << 24   # eps-mode sweeps of trains up to this many core elements keep the ranks on the device
 
 
-def _eps_deferred_ok(c, facs, rmax) -> bool:
-    """Non-batch (eps-mode) sweep: can every bond be enqueued without reading its rank back?  Only worth it where the
-    host synchronisations dominate (a small train: every kernel is latency-bound) AND the caller gave a rank cap (the
-    factors are computed at the cap: `round_tt(rmax=r)` on one tensor -- eps defaults to 1e-14, tensor.py:2008-2014 --
-    is the case this is for); only on the fused <= 64-row truncation kernels.  TTR_EPS_DEFERRED=1 / 0 forces / forbids it."""
+def _sweep_elems(shapes) -> int:
+    """Elements the L2R sweep of one train with cores ``shapes`` [(r0, I, r1), ...] factors: core mu enters as (k I) x r1 with
+    k = min(rows, columns) of the R factor before it."""
+    k, elems = shapes[0][0], 0
+    for r0, I, r1 in shapes:
+        elems += k * I * r1
+        k = min(k * I, r1)
+    return elems
+
+
+def _eps_deferred_policy(shapes, Bt: int, rmax) -> bool:
+    """Non-batch (eps-mode) sweep: may it keep its ranks on the device -- every bond enqueued at its rank cap, ONE readback of all
+    ranks at the end?  Only worth it where the host synchronisations dominate (a small train: every kernel is latency-bound)
+    AND the caller gave a rank cap (the factors are computed at the cap: `round_tt(rmax=r)` on one tensor -- eps defaults to
+    1e-14, tensor.py:2008-2014 -- is the case this is for).  TTR_EPS_DEFERRED=1 / 0 forces / forbids it (read at every call)."""
     mode = os.environ.get("TTR_EPS_DEFERRED", "auto")
-    if mode == "0":
+    if mode == "0" or Bt != 1:
         return False
-    N = len(c)
-    last = c[N - 1]
-    if last.shape[0] != 1 or any(isinstance(f[0], _ExplicitQ) for f in facs):
+    if mode == "1":
+        return True
+    # (without a rank cap every bond would be computed at its FULL rank: measured on config C2 -- rank 64 in, 32 out, no
+    # rmax -- 9.3 ms deferred against 8.3 ms with one readback per bond; with a cap the widths are those of the result)
+    return _sweep_elems(shapes) <= _EPS_DEFERRED_MAX_ELEMS and all(r is not None for r in rmax)
+
+
+def _eps_deferred_ok(c, facs, rmax) -> bool:
+    """``_eps_deferred_policy`` for the host loop, after its L2R sweep (``c[-1]``: the carry of the last core, ``facs``: (factors,
+    rows of R before the core, I) per earlier core), plus what only that loop knows: every Q is implicit and every bond goes
+    to the fused <= 64-row truncation kernels."""
+    last = c[-1]
+    if any(isinstance(f[0], _ExplicitQ) for f in facs):
         return False
-    elems = last.numel() + sum(f[0].m * f[0].n for f in facs)
-    if mode != "1" and (elems > _EPS_DEFERRED_MAX_ELEMS or any(r is None for r in rmax)):
-        # (without a rank cap every bond would be computed at its FULL rank: measured on config C2 -- rank 64 in, 32 out, no
-        # rmax -- 9.3 ms deferred against 8.3 ms with one readback per bond; with a cap the widths are those of the result)
+    shapes = [(rows_k, I, f.n) for f, rows_k, I in facs] + [tuple(last.shape[1:])]   # (f.m = rows_k I: the count of the C sweep)
+    if not _eps_deferred_policy(shapes, last.shape[0], rmax):
         return False
-    rn = last.shape[3]
-    for mu in range(N - 1, 0, -1):
-        m = last.shape[1] if mu == N - 1 else facs[mu][1]
-        I = last.shape[2] if mu == N - 1 else facs[mu][2]
-        n = I * rn
-        if m > 64 or m > n:
+    rn = shapes[-1][2]
+    for mu in range(len(c) - 1, 0, -1):   # bond mu: the carry is rows x (I rn)
+        rows, I, _ = shapes[mu]
+        if rows > 64 or rows > I * rn:
             return False
-        rn = _rank_cap(rmax[mu - 1], min(m, n))
+        rn = _rank_cap(rmax[mu - 1], rows)
     return True
 
 
