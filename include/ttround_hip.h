@@ -53,7 +53,7 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand and ttr_mode_scan / ttr_mode_reduce were ADDED under 17: no existing signature changed, and a library without the
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce and ttr_pce_design / ttr_pce_predict were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
@@ -968,6 +968,37 @@ int ttr_mode_scan(int dtype, int64_t R, int64_t I, int64_t C, const void* X, con
                   const int64_t* y_strides, void* stream);
 int ttr_mode_reduce(int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, const void* w, double scale,
                     void* Y, const int64_t* y_strides, void* stream);
+
+/*
+ * Sparse polynomial-chaos regression (added under ABI 17; interpolation.py:367-383 `PCEInterpolator._design_matrix`, a gather of a
+ * P x (C N) intermediate and a product there).  `Z` [P, N]: the centred features, elements of the dtype with
+ * the ELEMENT strides (sz0, sz1) -- a column slice of a wider matrix or a transposed view is read where it lies.  `Psi`
+ * [N, S, S] contiguous, of the dtype: column s of Psi[n] holds the monomial coefficients of basis polynomial s of mode n.
+ * `coords` [C, N] contiguous int64.  The basis value is B(p, n, s) = sum_k Z[p, n]^k Psi[n, k, s], by Horner from k = S - 1 down.
+ *
+ * ttr_pce_design    M[p ldm + c] = prod_n B(p, n, coords[c, n]), n increasing.  ldm >= C; nothing outside c < C is written.
+ * ttr_pce_predict   y[p] = sum_c coef[c] prod_n B(p, n, coords[c, n]), c increasing (one FMA per candidate).  `coef` [C] and
+ *                   `y` [P] contiguous, of the dtype.  The P x C matrix is never formed.
+ *
+ * A workgroup evaluates the N S basis values of a tile of points into LDS once (Psi staged in LDS in chunks of whole modes) and
+ * stages the coordinate table in LDS in tiles.  Every coordinate is checked as it is staged: one outside [0, S) makes its
+ * candidate's product 0 (whatever the basis values are) and ORs 1 into `flag` (one int32 on the device, zeroed by the caller; a
+ * plain store, every writer writes the same bit); no address is formed from an unchecked coordinate.  design: lane =
+ * candidate, a point's N S values contiguous in LDS (the gather over s <= 16 consecutive doubles touches distinct banks), the
+ * stores of a wave are 64 consecutive c of one row of M.  predict: lane = point, the tile stored [n S + s][point], coordinates and
+ * coefficients are wave-uniform reads.  Both dtypes compute in fp64 registers and round once, at the store.  No atomics, no
+ * workspace, no host synchronisation, workgroups never communicate; the tiling and with it the order of every product and sum
+ * follow from (P, N, S, C) and the dtype alone: the same call gives the same bits.
+ * Limits (host-only queries): S <= ttr_pce_max_order() (= 16), N S <= ttr_pce_max_basis() (= 256).  Before any launch, outputs
+ * untouched: TTR_E_INVALID for a bad dtype, a size < 1, a size above the limits, ldm < C or a null pointer.
+ * Profiling kind: TTR_PROF_MISC.
+ */
+int ttr_pce_max_order(void);
+int ttr_pce_max_basis(void);
+int ttr_pce_design(int dtype, int64_t P, int64_t N, int64_t S, int64_t C, const void* Z, int64_t sz0, int64_t sz1, const void* Psi,
+                   const void* coords, void* M, int64_t ldm, void* flag, void* stream);
+int ttr_pce_predict(int dtype, int64_t P, int64_t N, int64_t S, int64_t C, const void* Z, int64_t sz0, int64_t sz1, const void* Psi,
+                    const void* coords, const void* coef, void* y, void* flag, void* stream);
 
 #ifdef __cplusplus
 }

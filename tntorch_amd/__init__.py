@@ -5,7 +5,8 @@ that sit on the TT decomposition / rounding hot path: ``tn.Tensor``, ``tn.round_
 ``tn.round``, ``tn.truncated_svd``, the unfoldings, plus the small helpers the reference's
 tests use around them (``rand``/``randn``, ``dot``/``norm``/``relative_error``), and TT-cross (``tn.cross``, ``tn.maxvol``,
 ``tn.meshgrid`` and the element-wise functions of ``ops``: ``tn.exp``, ``tn.cos``, ...), and TT completion from samples
-(``tn.als_completion``), sparse TT-SVD (``tn.sparse_tt_svd``), the moment family (``tn.hadamard_sum``, ``tn.raw_moment``,
+(``tn.als_completion``), sparse TT-SVD (``tn.sparse_tt_svd``), sparse polynomial-chaos regression of scattered float samples
+(``tn.PCEInterpolator``, ``tn.gram_schmidt``, ``tn.features2indices``, ...), the moment family (``tn.hadamard_sum``, ``tn.raw_moment``,
 ``tn.normalized_moment``, ``tn.var``, ``tn.std``) and the differential operators of ``derivatives.py`` (``tn.partial``,
 ``tn.gradient``, ``tn.divergence``, ``tn.curl``, ``tn.laplacian``, ``tn.dgsm``, ``tn.active_subspace``) and the exact
 convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automata`` (``tn.weight_mask``, ``tn.accepted_inputs``,

@@ -1318,6 +1318,70 @@ def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float 
     return Y
 
 
+def pce_max_order() -> int:
+    """ttr_pce_max_order: the largest number S of basis polynomials per mode ttr_pce_design / ttr_pce_predict take."""
+    return int(lib().ttr_pce_max_order())
+
+
+def pce_max_basis() -> int:
+    """ttr_pce_max_basis: the largest N * S ttr_pce_design / ttr_pce_predict take."""
+    return int(lib().ttr_pce_max_basis())
+
+
+def _pce_args(who: str, Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, flag: Optional[torch.Tensor]):
+    if not (isinstance(Z, torch.Tensor) and Z.is_cuda and Z.dim() == 2):
+        raise ValueError("{}: Z must be a [P, N] device matrix".format(who))
+    P, N = Z.shape
+    if not (Psi.dim() == 3 and Psi.shape[0] == N and Psi.shape[1] == Psi.shape[2] and Psi.dtype == Z.dtype and Psi.device == Z.device
+            and Psi.is_contiguous()):
+        raise ValueError("{}: Psi must be a contiguous [N, S, S] tensor of Z's dtype on Z's device".format(who))
+    if not (coords.dim() == 2 and coords.shape[1] == N and coords.dtype == torch.int64 and coords.device == Z.device and coords.is_contiguous()):
+        raise ValueError("{}: coords must be a contiguous int64 [C, N] tensor on Z's device".format(who))
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=Z.device)
+    elif not (flag.dtype == torch.int32 and flag.numel() == 1 and flag.device == Z.device):
+        raise ValueError("{}: flag must be one int32 on Z's device".format(who))
+    return P, N, int(Psi.shape[1]), int(coords.shape[0]), flag
+
+
+@_on_device
+def pce_design(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, out: Optional[torch.Tensor] = None,
+               flag: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ttr_pce_design: M[p, c] = prod_n B(p, n, coords[c, n]) with B(p, n, s) = sum_k Z[p, n]^k Psi[n, k, s], for Z [P, N] (any
+    element strides), Psi [N, S, S] and coords [C, N] (int64).  ``out``: a [P, C] view with element strides (ldm, 1) that receives
+    the result; a fresh contiguous matrix when None.  Returns (M, flag): ``flag`` (one int32 on the device, zeroed here when not
+    given) has bit 0 set where a coordinate lay outside [0, S) -- that candidate's column is 0.  Nothing is read back."""
+    dt = dtype_code(Z.dtype)
+    P, N, S, C, flag = _pce_args("pce_design", Z, Psi, coords, flag)
+    if out is not None and not (tuple(out.shape) == (P, C) and out.dtype == Z.dtype and out.device == Z.device
+                                and (C <= 1 or out.stride(1) == 1) and (P <= 1 or out.stride(0) >= C)):
+        raise ValueError("pce_design: out must be a [P, C] view of Z's dtype with element strides (ldm >= C, 1)")
+    M = out if out is not None else torch.empty((P, C), dtype=Z.dtype, device=Z.device)
+    if P == 0 or C == 0:
+        return M, flag
+    ldm = int(M.stride(0)) if P > 1 else C
+    _call("ttr_pce_design", dt, P, N, S, C, Z.data_ptr(), int(Z.stride(0)), int(Z.stride(1)), Psi.data_ptr(), coords.data_ptr(),
+          M.data_ptr(), ldm, flag.data_ptr())
+    return M, flag
+
+
+@_on_device
+def pce_predict(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, coef: torch.Tensor,
+                flag: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ttr_pce_predict: y[p] = sum_c coef[c] prod_n B(p, n, coords[c, n]) (arguments as for ``pce_design``, ``coef`` [C]
+    contiguous, of Z's dtype); the P x C matrix is never formed.  Returns (y, flag).  Nothing is read back."""
+    dt = dtype_code(Z.dtype)
+    P, N, S, C, flag = _pce_args("pce_predict", Z, Psi, coords, flag)
+    if not (coef.dim() == 1 and coef.shape[0] == C and coef.dtype == Z.dtype and coef.device == Z.device and coef.is_contiguous()):
+        raise ValueError("pce_predict: coef must be a contiguous vector of {} elements of Z's dtype on Z's device".format(C))
+    if P == 0 or C == 0:
+        return torch.zeros(P, dtype=Z.dtype, device=Z.device), flag
+    y = torch.empty(P, dtype=Z.dtype, device=Z.device)
+    _call("ttr_pce_predict", dt, P, N, S, C, Z.data_ptr(), int(Z.stride(0)), int(Z.stride(1)), Psi.data_ptr(), coords.data_ptr(),
+          coef.data_ptr(), y.data_ptr(), flag.data_ptr())
+    return y, flag
+
+
 
 def core_convolve_max_taps() -> int:
     """ttr_core_convolve_max_taps: the terms of the sum ttr_core_convolve stages in LDS at once (longer sums are chunked)."""

@@ -1767,6 +1767,62 @@ def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float 
     return _hip.mode_reduce(X.contiguous(), None if w is None else w.contiguous(), scale, out)
 
 
+# ---------------------------------------------------------------------------------------------- polynomial chaos (interpolation.py:347-630)
+PCE_CHUNK = 1 << 20   # points per GEMM of pce_moments: the fp64 powers of a chunk are PCE_CHUNK x N x S
+
+
+def pce_limits() -> Tuple[int, int]:
+    """(largest S, largest N * S) of ttr_pce_design / ttr_pce_predict."""
+    return _hip.pce_max_order(), _hip.pce_max_basis()
+
+
+def pce_moments(Z: torch.Tensor, S: int) -> torch.Tensor:
+    """H[n] = V_n^T V_n / P with V_n[p, k] = Z[p, n]^k, [N, S, S] in fp64 on the device: one batched ttr_gemm over the modes per
+    chunk of PCE_CHUNK points (the powers are elementwise torch)."""
+    P, N = Z.shape
+    H = None
+    ks = torch.arange(S, device=Z.device)
+    for lo in range(0, P, PCE_CHUNK):
+        V = (Z[lo : lo + PCE_CHUNK].double().t()[:, :, None] ** ks).contiguous()   # [N, chunk, S]
+        G = _hip.gemm(V, V, transA=True)
+        H = G if H is None else H + G
+    return H / P
+
+
+def _pce_raise(flag: torch.Tensor, S: int):
+    if int(flag.item()) != 0:
+        raise ValueError("pce: coordinates outside [0, {})".format(S))
+
+
+def pce_design(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """interpolation.py:367-383 (ttr_pce_design): M[p, c] = prod_n B(p, n, coords[c, n]) in one launch; ``out`` may be a [P, C]
+    block of a wider matrix.  The flag is read back: ValueError for a coordinate outside [0, S)."""
+    M, flag = _hip.pce_design(Z, Psi.contiguous(), coords.long().contiguous(), out)
+    _pce_raise(flag, Psi.shape[1])
+    return M
+
+
+def pce_predict(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, coef: torch.Tensor, check: bool = True) -> torch.Tensor:
+    """interpolation.py:557-566 (ttr_pce_predict): y[p] = sum_c coef[c] prod_n B(p, n, coords[c, n]) in one launch, the P x C
+    matrix never formed.  ``check``: read the flag back and raise ValueError for a coordinate outside [0, S) (False: nothing is
+    read back; such a candidate contributes 0)."""
+    y, flag = _hip.pce_predict(Z, Psi.contiguous(), coords.long().contiguous(), coef.contiguous())
+    if check:
+        _pce_raise(flag, Psi.shape[1])
+    return y
+
+
+def pce_gram(M: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """[M | y]^T M as one [C + 1, C] matrix in M's dtype on the matrix cores (two ttr_gemm launches, split-K over the rows, into
+    one buffer): rows 0 .. C - 1 are M^T M, row C is M^T y; the caller copies it to the host once."""
+    C = M.shape[1]
+    M3 = M[None]
+    out = torch.empty((1, C + 1, C), dtype=M.dtype, device=M.device)
+    _hip.gemm(M3, M3, transA=True, out=out[:, :C])
+    _hip.gemm(y[None, :, None].contiguous(), M3, transA=True, out=out[:, C:])
+    return out[0]
+
+
 # ---------------------------------------------------------------------------------------------- convolution (tools.py:579-647)
 def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Tensor:
     """One core of the exact convolution train (ttr_core_convolve): a [R1, I, R2], c [S1, J, S2] -> [R1 S1, K, R2 S2], the window

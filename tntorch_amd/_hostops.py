@@ -424,6 +424,78 @@ def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float 
     return out
 
 
+# ---------------------------------------------------------------------------------------------- polynomial chaos (interpolation.py:347-630)
+PCE_CHUNK = 1 << 14   # points per pass of the mirrors below: the largest intermediate is PCE_CHUNK x max(C, N S) in fp64
+
+
+def _pce_check(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor):
+    if Z.dim() != 2 or Psi.dim() != 3 or Psi.shape[0] != Z.shape[1] or Psi.shape[1] != Psi.shape[2] or Psi.dtype != Z.dtype:
+        raise ValueError("pce: expected Z [P, N] and Psi [N, S, S] of one dtype")
+    if coords.dim() != 2 or coords.shape[1] != Z.shape[1] or coords.dtype.is_floating_point:
+        raise ValueError("pce: coords must be an integer [C, N] matrix")
+    S = int(Psi.shape[1])
+    if coords.numel() and (int(coords.min()) < 0 or int(coords.max()) >= S):
+        raise ValueError("pce: coordinates outside [0, {})".format(S))
+
+
+def _pce_basis(Z: torch.Tensor, Psi: torch.Tensor) -> torch.Tensor:
+    """B[p, n, s] = sum_k Z[p, n]^k Psi[n, k, s] in fp64, by Horner from k = S - 1 down (the order of the kernels)."""
+    Zd, Pd = Z.double()[:, :, None], Psi.double()
+    S = Pd.shape[1]
+    acc = Pd[None, :, S - 1, :].expand(Zd.shape[0], -1, -1)
+    for k in range(S - 2, -1, -1):
+        acc = acc * Zd + Pd[None, :, k, :]
+    return acc
+
+
+def pce_moments(Z: torch.Tensor, S: int) -> torch.Tensor:
+    """H[n] = V_n^T V_n / P with V_n[p, k] = Z[p, n]^k: the empirical moment matrices [N, S, S] of the columns of Z, in fp64."""
+    P, N = Z.shape
+    H = torch.zeros(N, S, S, dtype=torch.float64, device=Z.device)
+    ks = torch.arange(S, device=Z.device)
+    for lo in range(0, P, PCE_CHUNK):
+        V = Z[lo : lo + PCE_CHUNK].double().t()[:, :, None] ** ks   # [N, chunk, S]
+        H += _t(V) @ V
+    return H / P
+
+
+def _pce_products(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor):
+    """(first row, fp64 products [rows, C]) of one chunk of PCE_CHUNK points after the other: no P x C x N intermediate."""
+    _pce_check(Z, Psi, coords)
+    coords = coords.long()
+    for lo in range(0, Z.shape[0], PCE_CHUNK):
+        B = _pce_basis(Z[lo : lo + PCE_CHUNK], Psi)
+        prod = B[:, 0, :][:, coords[:, 0]]
+        for n in range(1, Z.shape[1]):
+            prod = prod * B[:, n, :][:, coords[:, n]]
+        yield lo, prod
+
+
+def pce_design(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mirror of ttr_pce_design: M[p, c] = prod_n B(p, n, coords[c, n]) for Z [P, N], Psi [N, S, S], coords [C, N], computed in
+    fp64 (n increasing) and rounded once.  ValueError for a coordinate outside [0, S).  ``out`` (a [P, C] view) receives the
+    result."""
+    M = out if out is not None else torch.empty((Z.shape[0], coords.shape[0]), dtype=Z.dtype, device=Z.device)
+    for lo, prod in _pce_products(Z, Psi, coords):
+        M[lo : lo + PCE_CHUNK] = prod.to(Z.dtype)
+    return M
+
+
+def pce_predict(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor, coef: torch.Tensor, check: bool = True) -> torch.Tensor:
+    """Mirror of ttr_pce_predict: y[p] = sum_c coef[c] prod_n B(p, n, coords[c, n]), in fp64 and rounded once."""
+    y = torch.empty(Z.shape[0], dtype=Z.dtype, device=Z.device)
+    cd = coef.double()
+    for lo, prod in _pce_products(Z, Psi, coords):
+        y[lo : lo + PCE_CHUNK] = (prod @ cd).to(Z.dtype)
+    return y
+
+
+def pce_gram(M: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """[M | y]^T M as one [C + 1, C] matrix in M's dtype: rows 0 .. C - 1 are the Gram matrix M^T M, row C is M^T y -- all that
+    LARS needs of the P rows, in one tensor (one copy to the host)."""
+    return torch.cat([M.t() @ M, (y @ M)[None]], dim=0)
+
+
 # ---------------------------------------------------------------------------------------------- convolution (tools.py:579-647)
 def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Tensor:
     """Mirror of ttr_core_convolve: a [R1, I, R2], c [S1, J, S2] -> [R1 S1, K, R2 S2],
