@@ -53,7 +53,7 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce and ttr_pce_design / ttr_pce_predict were ADDED under 17: no existing signature changed, and a library without the
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict and ttr_mode_sandwich were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
@@ -999,6 +999,33 @@ int ttr_pce_design(int dtype, int64_t P, int64_t N, int64_t S, int64_t C, const 
                    const void* coords, void* M, int64_t ldm, void* flag, void* stream);
 int ttr_pce_predict(int dtype, int64_t P, int64_t N, int64_t S, int64_t C, const void* Z, int64_t sz0, int64_t sz1, const void* Psi,
                     const void* coords, const void* coef, void* y, void* flag, void* stream);
+
+/*
+ * The centred, weighted sandwich of the ANOVA / Sobol environment recursion (added under ABI 17; anova.py:99-148 `sobol`, computed
+ * from environments instead of masked extended trains), on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64
+ * (true fp32 / fp64 operands and accumulators):
+ *
+ * ttr_mode_sandwich   Q[s, c, c'] = sum_i w[i] sum_{a, b} (A[a, i, c] - mu[a, c]) Z[s, a, b] (A[b, i, c'] - mu[b, c'])
+ *
+ * `Z` [S, R, R] contiguous (it need not be symmetric), `A` [R, I, C] contiguous -- its 3 element strides are passed as a HOST
+ * array and checked (the stride of an extent-1 axis is free) --, `w` [I] contiguous or NULL (all ones), `mu` [R, C] contiguous or
+ * NULL (zeros), `Q` [S, C, C] contiguous; all device elements of the dtype.  mu^T Z[s] mu is the same entry with mu as the core
+ * [R, 1, C] and `w`, `mu` NULL.  A - mu is formed in the registers that carry the load: no centred copy of the core and no
+ * [S, I, R, C] intermediate is written; Y = Z[s] (A_i - mu) stays in accumulator registers and is the operand of the second product.
+ * One workgroup owns one s and one contiguous chunk of i (the chunk length follows from (S, I) alone: at least 8, and longer where
+ * S ceil(I / 8) exceeds 512 workgroups); with nsplit = ceil(I / chunk) > 1 the chunks' sums go to [S, nsplit, C C] in `workspace`
+ * (ttr_mode_sandwich_workspace_bytes, 0 for one chunk; TTR_E_* (< 0) where the entry would refuse the sizes) and ttr_mode_reduce
+ * adds them in chunk order.  No atomics, workgroups never communicate, no host synchronisation, 64-bit indices: the same call
+ * gives the same bits.
+ * Limits: R, C <= ttr_mode_sandwich_max_rank() (= 64; host-only query), S <= 65535; beyond them TTR_E_UNSUPPORTED.  Before any
+ * launch, with Q untouched: TTR_E_INVALID for a bad dtype, an extent < 1, a null Z / A / Q / a_strides or a Q that is one of the
+ * inputs; TTR_E_UNSUPPORTED for a non-contiguous A; TTR_E_WORKSPACE for a missing or short workspace.
+ * Profiling kind: TTR_PROF_MISC.
+ */
+int ttr_mode_sandwich_max_rank(void);
+int64_t ttr_mode_sandwich_workspace_bytes(int dtype, int64_t S, int64_t R, int64_t I, int64_t C);
+int ttr_mode_sandwich(int dtype, int64_t S, int64_t R, int64_t I, int64_t C, const void* Z, const void* A, const int64_t* a_strides,
+                      const void* w, const void* mu, void* Q, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

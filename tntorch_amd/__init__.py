@@ -13,7 +13,8 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ...), ``tn.logic`` (``tn.symbols``, ``tn.only``, ``tn.implies``, ...), ``tn.mask`` and ``tn.partialset``, and the array tools of
 ``tools.py`` and ``ops.py``: ``tn.squeeze``, ``tn.unsqueeze``, ``tn.unbind``, ``tn.cat``, ``tn.transpose``, ``tn.flip``, ``tn.pad``,
 ``tn.ttm``, ``tn.generate_basis`` and ``tn.cumsum`` (marginalising a mode is ``tn.squeeze(tn.ttm(t, weights, dim))``; there is no
-``tn.sum`` / ``tn.mean``).
+``tn.sum`` / ``tn.mean``), and the variance-based sensitivity analysis of ``anova.py``: ``tn.anova_decomposition``,
+``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``.
 """
 
 from .tools import *  # noqa: F401,F403
@@ -29,6 +30,7 @@ from .interpolation import *  # noqa: F401,F403
 from .derivatives import *  # noqa: F401,F403
 from .automata import *  # noqa: F401,F403
 from .logic import *  # noqa: F401,F403
+from .anova import *  # noqa: F401,F403
 from . import automata, logic  # noqa: F401
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401

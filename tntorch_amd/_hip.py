@@ -1318,6 +1318,42 @@ def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float 
     return Y
 
 
+def mode_sandwich_max_rank() -> int:
+    """ttr_mode_sandwich_max_rank: the largest R and C ttr_mode_sandwich takes."""
+    return int(lib().ttr_mode_sandwich_max_rank())
+
+
+def mode_sandwich_workspace_bytes(dt: torch.dtype, S: int, R: int, I: int, C: int) -> int:
+    """ttr_mode_sandwich_workspace_bytes; a negative status (the entry would refuse these sizes) is returned."""
+    return int(lib().ttr_mode_sandwich_workspace_bytes(dtype_code(dt), int(S), int(R), int(I), int(C)))
+
+
+@_on_device
+def mode_sandwich(Z: torch.Tensor, A: torch.Tensor, w: Optional[torch.Tensor] = None, mu: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_mode_sandwich: Z [S, R, R] (contiguous), A [R, I, C], w [I] or None (ones), mu [R, C] or None (zeros) -> Q [S, C, C],
+    Q[s] = sum_i w[i] (A_i - mu)^T Z[s] (A_i - mu).  A is passed with the strides it has: the library refuses anything but
+    contiguous ones.  ``workspace``: a uint8 device tensor of at least mode_sandwich_workspace_bytes(...) bytes (allocated here
+    when None)."""
+    dt = dtype_code(Z.dtype)
+    assert Z.dim() == 3 and A.dim() == 3 and Z.is_contiguous() and A.dtype == Z.dtype and A.device == Z.device
+    S, R, _ = Z.shape
+    _, I, C = A.shape
+    assert Z.shape[2] == R and A.shape[0] == R
+    if w is not None and not (w.dim() == 1 and w.shape[0] == I and w.dtype == Z.dtype and w.device == Z.device and w.is_contiguous()):
+        raise ValueError("mode_sandwich: w must be a contiguous vector of {} elements of Z's dtype on Z's device".format(I))
+    if mu is not None and not (tuple(mu.shape) == (R, C) and mu.dtype == Z.dtype and mu.device == Z.device and mu.is_contiguous()):
+        raise ValueError("mode_sandwich: mu must be a contiguous [{}, {}] matrix of Z's dtype on Z's device".format(R, C))
+    wsb = mode_sandwich_workspace_bytes(Z.dtype, S, R, I, C)
+    if wsb < 0:
+        _check(wsb, "ttr_mode_sandwich_workspace_bytes")
+    ws = workspace if workspace is not None else _workspace(wsb, Z.device)
+    Q = torch.empty((S, C, C), dtype=Z.dtype, device=Z.device)
+    _call("ttr_mode_sandwich", dt, S, R, I, C, Z.data_ptr(), A.data_ptr(), _i64(A.stride()), _ptr(w), _ptr(mu), Q.data_ptr(), _ptr(ws),
+          int(ws.numel()) if ws is not None else 0)
+    return Q
+
+
 def pce_max_order() -> int:
     """ttr_pce_max_order: the largest number S of basis polynomials per mode ttr_pce_design / ttr_pce_predict take."""
     return int(lib().ttr_pce_max_order())

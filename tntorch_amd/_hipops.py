@@ -1767,8 +1767,37 @@ def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float 
     return _hip.mode_reduce(X.contiguous(), None if w is None else w.contiguous(), scale, out)
 
 
+# ---------------------------------------------------------------------------------------------- ANOVA / Sobol (anova.py:99-148)
+# Ranks (the larger of R and C) up to which mode_sandwich takes the fused kernel; above it, and above the kernel's own limit, the
+# hsum_step(K = 3) route.  The kernel's own limit: the fused launch won at every rank tools/anova_bench.py measured, 8x at the least
+# (profiles/anova_bench_mi355x.jsonl).
+SANDWICH_FUSED_MAX_RANK = 64
+
+
+def mode_sandwich(Z: torch.Tensor, A: torch.Tensor, w: Optional[torch.Tensor] = None, mu: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """anova.py:99-148 as an environment step: Z [S, R, R], A [R, I, C], w [I] or None (ones), mu [R, C] or None (zeros) ->
+    Q [S, C, C], Q[s] = sum_i w[i] (A_i - mu)^T Z[s] (A_i - mu).  One ttr_mode_sandwich launch (plus the reduction of its
+    partials) up to rank min(SANDWICH_FUSED_MAX_RANK, ttr_mode_sandwich_max_rank()); above it one ttr_hsum_step with K = 3 per s
+    on a centred copy of the core, which works at any rank."""
+    R, I, C = A.shape
+    if max(R, C) <= min(SANDWICH_FUSED_MAX_RANK, _hip.mode_sandwich_max_rank()):
+        return _hip.mode_sandwich(Z.contiguous(), A.contiguous(), None if w is None else w.contiguous(),
+                                  None if mu is None else mu.contiguous())
+    return mode_sandwich_hsum(Z, A, w, mu)
+
+
+def mode_sandwich_hsum(Z: torch.Tensor, A: torch.Tensor, w: Optional[torch.Tensor] = None, mu: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mode_sandwich through ttr_hsum_step: cores (A - mu, w as [1, I, 1], A - mu) on the interface Z[s] read as [R, 1, R]; the
+    intermediate [I, C, 1, R] goes through the entry's workspace."""
+    R, I, C = A.shape
+    Ac = (A if mu is None else A - mu[:, None, :]).contiguous()
+    wc = (A.new_ones(I) if w is None else w).reshape(1, I, 1).contiguous()
+    Zc = Z.contiguous()
+    return torch.stack([hsum_step(Zc[s].reshape(R, 1, R), [Ac, wc, Ac]).reshape(C, C) for s in range(Z.shape[0])])
+
+
 # ---------------------------------------------------------------------------------------------- polynomial chaos (interpolation.py:347-630)
-PCE_CHUNK = 1 << 20   # points per GEMM of pce_moments: the fp64 powers of a chunk are PCE_CHUNK x N x S
+PCE_CHUNK = 1 << 20  # points per GEMM of pce_moments: the fp64 powers of a chunk are PCE_CHUNK x N x S
 
 
 def pce_limits() -> Tuple[int, int]:

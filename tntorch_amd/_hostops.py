@@ -424,8 +424,19 @@ def mode_reduce(X: torch.Tensor, w: Optional[torch.Tensor] = None, scale: float 
     return out
 
 
+# ---------------------------------------------------------------------------------------------- ANOVA / Sobol (anova.py:99-148)
+def mode_sandwich(Z: torch.Tensor, A: torch.Tensor, w: Optional[torch.Tensor] = None, mu: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mirror of ttr_mode_sandwich: Z [S, R, R], A [R, I, C], w [I] or None (ones), mu [R, C] or None (zeros) -> Q [S, C, C],
+    Q[s] = sum_i w[i] (A_i - mu)^T Z[s] (A_i - mu): two einsums in the input dtype."""
+    Ac = A if mu is None else A - mu[:, None, :]
+    Y = torch.einsum("sab,bic->saic", Z, Ac)
+    if w is not None:
+        Y = Y * w[None, None, :, None]
+    return torch.einsum("aic,said->scd", Ac, Y)
+
+
 # ---------------------------------------------------------------------------------------------- polynomial chaos (interpolation.py:347-630)
-PCE_CHUNK = 1 << 14   # points per pass of the mirrors below: the largest intermediate is PCE_CHUNK x max(C, N S) in fp64
+PCE_CHUNK = 1 << 14  # points per pass of the mirrors below: the largest intermediate is PCE_CHUNK x max(C, N S) in fp64
 
 
 def _pce_check(Z: torch.Tensor, Psi: torch.Tensor, coords: torch.Tensor):
