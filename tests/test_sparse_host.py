@@ -4,6 +4,7 @@ The golden data (tests/golden/sparse_tt_svd_f64.npz, tools/gen_sparse_golden.py)
 """
 import ctypes
 import json
+import math
 import os
 
 import numpy as np
@@ -11,7 +12,7 @@ import pytest
 import torch
 
 import tntorch_amd as tn
-from tntorch_amd import _hip
+from tntorch_amd import _hip, _hostops
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "sparse_tt_svd_f64.npz")
@@ -204,3 +205,144 @@ def test_sparse_entries_argument_envelope(cabi):
         assert project(dt, 3, 5, 0, 10, 4) == INVALID and project(dt, 3, 5, 2, 3, 4) == INVALID
     assert gram(2, 3, 5, 10, 4) == INVALID and project(2, 3, 5, 2, 10, 4) == INVALID
     assert cabi.ttr_sparse_gram_parts(2, 3, 5, 10) == INVALID
+
+
+# ------------------------------------------------------------------- the references and case lists of tests/sparse_cases.py
+import sparse_cases as sc  # noqa: E402
+
+
+def small_tables():
+    yield sc.block_table([[0, 2], [], [1], [0, 1, 2], [2]], 2, torch.float64, 1)
+    yield sc.block_table([[3]], 1, torch.float32, 2, I=5)
+    yield sc.gram_table("passes_33", torch.float32)[0]
+    yield sc.gram_table("passes_ragged_50", torch.float64)[0]
+    yield sc.gram_table("geometry_Jt7", torch.float32)[0]
+    yield sc.project_table("empty_columns", torch.float64)[0]
+
+
+def test_block_table_against_loops():
+    """colptr / blkcol / D element by element, D D^T as the column-by-column sum of the header's formula, and the two longest-sum
+    lengths by counting."""
+    for t in small_tables():
+        r, I, C = t.r, t.I, t.C
+        assert t.V.shape == (t.nb, r) and t.D.shape == (r * I, C) and t.D.dtype == torch.float64 and t.colptr.tolist()[-1] == t.nb
+        D = [[0.0] * C for _ in range(r * I)]
+        G = [[0.0] * (r * I) for _ in range(r * I)]
+        holds = [set() for _ in range(I)]
+        longest = 0
+        for c in range(C):
+            blocks = range(int(t.colptr[c]), int(t.colptr[c + 1]))
+            longest = max(longest, len(blocks))
+            for b in blocks:
+                i = int(t.blk_i[b])
+                assert int(t.blkcol[b]) == c
+                holds[i].add(c)
+                for a in range(r):
+                    D[a * I + i][c] = float(t.V[b, a])
+                for bp in blocks:  # G[(a,i),(b,j)] += V_ci[a] V_cj[b] over the columns that hold both
+                    j = int(t.blk_i[bp])
+                    for a in range(r):
+                        for a2 in range(r):
+                            G[a * I + i][a2 * I + j] += float(t.V[b, a]) * float(t.V[bp, a2])
+        assert torch.equal(t.D, torch.tensor(D, dtype=torch.float64).reshape(r * I, C))
+        ref = t.D @ t.D.t()
+        G = torch.tensor(G, dtype=torch.float64)
+        assert float((ref - G).abs().max()) <= 64 * 2.0**-53 * float(ref.abs().max())  # sums of at most 50 products, two orders
+        assert t.gram_len == max(len(holds[i] & holds[j]) for i in range(I) for j in range(I))
+        assert t.project_len == r * longest
+
+
+def test_group_reference_against_a_loop():
+    for nb, I, kind in [(0, 3, "random"), (1, 1, "random"), (300, 7, "random"), (300, 7, "one_index"), (500, 20, "out_of_range")]:
+        b = sc.group_input(nb, I, kind).tolist()
+        ilist, iptr = sc.group_reference(b, I)
+        order, ptr = [], [0]
+        for i in range(I):
+            order += [k for k, v in enumerate(b) if v == i]
+            ptr.append(len(order))
+        assert ilist.tolist() == order and iptr.tolist() == ptr
+        if kind == "out_of_range":
+            assert len(order) < nb and set(b) - set(range(I)) == {I, I + 1}
+
+
+def test_keys_and_levels_references_against_loops():
+    for shape in (sc.KEYS_SHAPES[1], sc.KEYS_SHAPES[4], sc.KEYS_BIG_SHAPE):
+        X = sc.keys_input(shape, 3, P=40, corners=len(shape) == 3)
+        keys = sc.keys_reference(X, shape)
+        weights = [math.prod(shape[:n]) for n in range(len(shape))]  # x_1 minor
+        assert keys == [sum(int(x) * w for x, w in zip(row, weights)) for row in X.tolist()]
+        assert all(0 <= k < math.prod(shape) for k in keys)
+        # the key order is the order of the reversed tuples
+        assert sorted(range(40), key=lambda p: keys[p]) == sorted(range(40), key=lambda p: (X[p].tolist()[::-1], p))
+    for N in (1, 4):
+        for rotation in range(N):
+            levs = sc.level_sequence(N, rotation)
+            Xs = sc.sorted_set(levs, N, 5)
+            rows = Xs.tolist()
+            assert all(a[::-1] < b[::-1] for a, b in zip(rows, rows[1:]))  # strictly ascending, x_N major
+            brute = [N] + [max([n + 1 for n in range(N) if a[n] != b[n]], default=0) for a, b in zip(rows, rows[1:])]
+            assert sc.levels_reference(Xs.numpy()).tolist() == brute == levs
+            X, perm = sc.shuffled(Xs, 6)
+            assert torch.equal(X[perm.long()], Xs)
+    Xs[256] = Xs[255]
+    assert sc.levels_reference(Xs.numpy())[256] == 0
+    edges = {p: {sc.level_sequence(4, s)[p] for s in range(4)} for p in sc.LEVEL_EDGES}
+    assert all(v == {1, 2, 3, 4} for v in edges.values())  # every edge sees every level
+
+
+@pytest.mark.parametrize("name", list(sc.CANONICAL_CASES))
+def test_host_canonical_against_sorted_tuples(name):
+    shape, P = sc.CANONICAL_CASES[name]
+    X = sc.distinct_positions(shape, P, 100 + len(name))
+    rows = X.tolist()
+    assert len(set(map(tuple, rows))) == P and all(0 <= x < s for row in rows for x, s in zip(row, shape))
+    perm, lev = _hostops.sparse_canonical(X, shape)
+    assert perm.dtype == torch.int32 and lev.dtype == torch.int32
+    assert perm.tolist() == sorted(range(P), key=lambda p: rows[p][::-1])
+    assert lev.tolist() == sc.levels_reference(X[perm.long()].numpy()).tolist()
+    if math.prod(shape) < 2**63:  # the order of the linear keys, where they fit
+        keys = sc.keys_reference(X, shape)
+        assert perm.tolist() == sorted(range(P), key=lambda p: keys[p])
+
+
+def test_case_lists_build_valid_tables():
+    for name, (r, I, cols, parts) in sc.GRAM_CASES.items():
+        assert sc.valid_columns(cols, I) and all(len(c) > 0 for c in cols), name
+        nb = sum(len(c) for c in cols)
+        assert parts == sc.gram_parts(I, nb) and (parts > 1) == (name in sc.PARTS_CASES), name
+        lens = [sum(i in c for c in cols) for i in range(I)]
+        if name.startswith("passes"):
+            assert min(lens) > sc.KCH and all(len(c) >= 2 for c in cols), (name, lens)  # several passes, partners everywhere
+    lens = {n: [sum(i in c for c in sc.GRAM_CASES[n][2]) for i in range(sc.GRAM_CASES[n][1])] for n in sc.GRAM_CASES}
+    assert lens["passes_33"] == [33] * 3 and lens["passes_64"] == [64] * 3 and lens["passes_65"] == [65] * 3
+    assert lens["passes_ragged_50"] == [33, 33, 34] and lens["passes_ragged_98"] == [65, 65, 66]
+    assert lens["parts_short_absent"] == [5124, 5122, 4, 1, 0] and sum(lens["parts_short_absent"]) > 2048 * 5
+    assert sum(lens["parts_partners"]) == 4098 and sum(lens["parts_cap"]) > 16 * 2048 * 2
+    for name in ("geometry_I200", "geometry_I130"):
+        r, I, cols, _ = sc.GRAM_CASES[name]
+        assert len(cols) == 42 and sum(len(c) == I for c in cols) == 2 and -(-I // 64) >= 3  # column scans of three strides
+    for name, (cols, q) in sc.PROJECT_CASES.items():
+        assert sc.valid_columns(cols, sc.PROJECT_I) and 1 <= q <= sc.PROJECT_R * sc.PROJECT_I, name
+        assert all(len(c) > 0 for c in cols) or name == "empty_columns"
+    assert sorted(len(c) for c, q in sc.PROJECT_CASES.values() if q == 7) == [1, 23, 35, 36, 37, 40] and sc.project_cpw(7) == 36
+    assert sorted(len(c) for c, q in sc.PROJECT_CASES.values() if q == 1) == [23, 255, 256, 257] and sc.project_cpw(1) == 256
+    assert [sc.canonical_branch(s) for s, _ in sc.CANONICAL_CASES.values()] == ["int32", "int32", "int64", "no_keys"]
+    for name in sc.END_TO_END_CASES:
+        shape = sc.END_TO_END_CASES[name][0]
+        X, y, Z = sc.end_to_end_samples(name)
+        assert sc.canonical_branch(shape) == name and X.shape == (300, len(shape)) == Z.shape
+        rows = set(map(tuple, X.tolist()))
+        assert len(rows) == 300 and not rows & set(map(tuple, Z.tolist()))
+        assert all(0 <= int(A[:, n].min()) and int(A[:, n].max()) < shape[n] for A in (X, Z) for n in range(len(shape)))
+        t = tn.sparse_tt_svd(X, y, 1e-6, shape=shape)  # the CPU mirror: a rank-2 tensor, zero off the grid
+        assert max(int(r) for r in t.ranks_tt) == 2
+        assert float(torch.norm(sc.evaluate(t.cores, X) - y) / torch.norm(y)) <= 1e-6 and float(torch.norm(sc.evaluate(t.cores, Z)) / torch.norm(y)) <= 1e-6
+
+
+def test_declared_part_counts_match_the_library(cabi):
+    for name, (r, I, cols, parts) in sc.GRAM_CASES.items():
+        nb = sum(len(c) for c in cols)
+        for dt in (_hip.F32, _hip.F64):
+            assert cabi.ttr_sparse_gram_parts(dt, r, I, nb) == parts, name
+    assert cabi.ttr_sparse_group_workspace_bytes(*sc.GROUP_BIG) == 966 * 3 * 4
+    assert cabi.ttr_sparse_group_workspace_bytes(4194304, 3) == 1024 * 3 * 4  # chunks of 4096 blocks up to here
