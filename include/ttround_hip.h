@@ -694,7 +694,7 @@ int ttr_prof_collect_work(double* flops, double* bytes);
  * Both paths give bitwise identical values, and a point's value does not depend on the other points of the call.
  * Every index is validated on the device first: the int32 word at `oob_flag` (device) is set to 1 when an index lies outside
  * [-I_n, I_n), and to 0 otherwise; when set, nothing else is written.  The caller reads the word after the call.
- * Ranks <= 512, batch <= 65535.
+ * Ranks <= 512, batch <= 65535.  P == 0 clears the word and returns; `out` and the index columns may then be NULL.
  */
 int64_t ttr_gather_chain_workspace_bytes(int dtype, int64_t nmodes, const int64_t* ranks, const int64_t* sizes, int64_t P,
                                          int64_t batch);

@@ -357,7 +357,8 @@ extern "C" int ttr_gather_chain(int dtype, int64_t nmodes, int64_t batch, int64_
     TTR_REQUIRE(ranks[n] >= 1, TTR_E_INVALID, "ttr_gather_chain: rank %lld < 1", (long long)ranks[n]);
   for (int64_t n = 0; n < nmodes; ++n) {
     TTR_REQUIRE(sizes[n] >= 1, TTR_E_INVALID, "ttr_gather_chain: mode size %lld < 1", (long long)sizes[n]);
-    TTR_REQUIRE(cores[n] && idx[n], TTR_E_INVALID, "ttr_gather_chain: NULL core or index column %lld", (long long)n);
+    // an empty device tensor has a null data pointer: with P == 0 no index column is read
+    TTR_REQUIRE(cores[n] && (idx[n] || P == 0), TTR_E_INVALID, "ttr_gather_chain: NULL core or index column %lld", (long long)n);
     TTR_REQUIRE(sizes[n] < (int64_t)1 << 31, TTR_E_UNSUPPORTED, "ttr_gather_chain: mode size %lld", (long long)sizes[n]);
   }
   for (int64_t n = 0; n <= nmodes; ++n)
