@@ -1,16 +1,15 @@
-// What crosses translation units inside libttround_hip.so and is not in ttr_common.h: the prototypes of the dispatchers the
-// extern "C" wrappers call, the knob globals ttr_debug_set_knob writes, and two host helpers.
+// What the translation units of libttround_hip.so share on the host and ttr_common.h does not hold: the prototypes of the
+// dispatchers the extern "C" wrappers call, the knob globals ttr_debug_set_knob writes, and the host helpers of the entries
+// (dtype checks and dispatch, stride and alignment tests, the argument checks of a core [R, I, C]).
 //
 // HOST-ONLY: no __global__ / __device__ code and no template a kernel instantiates.  Including this file therefore cannot
 // alter any kernel, which is why it may live outside the set of files bench.py hashes (csrc/*.h and the kernel sources:
 // `source_sha` / `KIND_SOURCES`, which tie the counters of profiles/pmc_latest.json to the build they were taken from).
+// What device code shares (Pack, block_sum, the wave reductions) lives in ttr_common.h.
 //
-// Included by ttr_api.hip, ttr_orth.hip and ttr_vec.hip (the callers) and by ttr_cp.hip and ttr_eigsel.hip (which define
-// dispatchers declared here: the compiler checks declaration against definition there).
-// FOLLOW-UP, the next time the counters are re-collected: ttr_qr.hip, ttr_sweep.hip, ttr_eigh.hip, ttr_gemm.hip and
-// ttr_bjacobi.hip define the rest of these dispatchers and knobs and should include this file too; until then a changed
-// signature in one of them shows up at link time only.  (block_sum, which ttr_vec.hip and ttr_orth.hip both carry, moves into
-// ttr_common.h on the same occasion.)
+// Included by EVERY .hip file of the library: a unit that defines a dispatcher or a knob declared here has its definition
+// checked against the declaration by the compiler (default arguments stand here, on the declaration, only), and a unit with
+// extern "C" entries takes its checks and its dtype dispatch from the helpers at the end instead of carrying copies.
 #pragma once
 #include "../ttr_common.h"
 
@@ -118,10 +117,59 @@ extern int g_jacobi_live_wave;
 extern int g_eigh_small;
 extern int g_orth_rounds, g_orth_v2, g_orth_split;   // ttr_orth.hip
 
-inline bool dtype_ok(int dtype) { return dtype == TTR_F32 || dtype == TTR_F64; }
-
 // the census counters of ttr_prof_enable(2) ([2 * TTR_PROF_NKINDS]: flops per kind, then bytes per kind) for kernels that count
 // their own work; nullptr unless work_census_on()
 double* work_census_dev();
+
+// ------------------------------------------------------------------ host helpers of the extern "C" entries
+inline bool dtype_ok(int dtype) { return dtype == TTR_F32 || dtype == TTR_F64; }
+inline int64_t elem_size(int dtype) { return dtype == TTR_F32 ? 4 : 8; }  // bytes; of a dtype that passed dtype_ok
+
+// f(float{}) or f(double{}), and what it returns: for an entry whose two dtypes run the float or the double instance of ONE
+// template with the same arguments (`using T = decltype(t)` inside the generic lambda)
+template <typename F>
+auto by_dtype(int dtype, F&& f) -> decltype(f(float{})) {
+  if (dtype == TTR_F32) return f(float{});
+  return f(double{});
+}
+
+// element strides of a contiguous tensor of these extents?  (the stride of an extent-1 axis is never used: anything goes)
+inline bool contiguous(const int64_t* shape, const int64_t* strides, int nd) {
+  int64_t want = 1;
+  for (int d = nd - 1; d >= 0; --d) {
+    if (shape[d] != 1 && strides[d] != want) return false;
+    want *= shape[d];
+  }
+  return true;
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
+
+// The checks of an entry `who` that reads one contiguous core X [R, I, C] and writes another buffer: dtype, sizes, pointers, the
+// strides of X, the index envelope.  `rest`: the entry's other pointers that must not be null, tested with X and `out`;
+// `out_name`: what the message calls the output.
+inline int core_check(const char* who, int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides,
+                      const void* out, const char* out_name, bool rest = true) {
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
+  TTR_REQUIRE(R >= 1 && I >= 1 && C >= 1, TTR_E_INVALID, "%s: bad sizes R = %lld, I = %lld, C = %lld", who, (long long)R, (long long)I,
+              (long long)C);
+  TTR_REQUIRE(X && x_strides && out && rest, TTR_E_INVALID, "%s: null pointer", who);
+  TTR_REQUIRE(X != out, TTR_E_INVALID, "%s: X and %s must be different buffers", who, out_name);
+  const int64_t xs[3] = {R, I, C};
+  TTR_REQUIRE(contiguous(xs, x_strides, 3), TTR_E_UNSUPPORTED, "%s: X must be contiguous", who);
+  TTR_REQUIRE((double)R * (double)I * (double)C < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "%s: core too large", who);
+  return TTR_OK;
+}
+
+// Y [R, I, C] with element strides (sr, si, 1), rows and slabs that do not overlap; the stride of an extent-1 axis is free
+inline int strided_y_check(const char* who, int64_t R, int64_t I, int64_t C, const int64_t* y_strides, int64_t* sr, int64_t* si) {
+  *si = I > 1 ? y_strides[1] : C;
+  *sr = R > 1 ? y_strides[0] : I * *si;
+  TTR_REQUIRE((C == 1 || y_strides[2] == 1) && *si >= C && *sr >= I * *si, TTR_E_UNSUPPORTED,
+              "%s: Y needs element strides (sr, si, 1) with si >= C and sr >= I si", who);
+  TTR_REQUIRE((double)R * (double)*sr < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "%s: Y too large", who);
+  return TTR_OK;
+}
 
 }  // namespace ttr

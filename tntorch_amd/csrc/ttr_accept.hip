@@ -25,7 +25,7 @@
 // at idx[k], which is checked against [0, P I) (outside: the slot is skipped and TTR_ACCEPT_BAD_INDEX is ORed).  The search
 // terminates with 0 <= k < K for any content of offnew.  All stores are plain 8-byte vector stores; the word is ORed with one
 // vector atomic, only where a check fails.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -160,7 +160,7 @@ using namespace ttr;
 extern "C" int ttr_accept_max_rank(void) { return kMaxRank; }
 
 extern "C" int ttr_accept_count(int dtype, int64_t P, int64_t r, int64_t I, const void* L, const void* fiber, void* C, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_accept_count: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_accept_count: bad dtype %d", dtype);
   TTR_REQUIRE(P >= 1 && r >= 1 && I >= 1, TTR_E_INVALID, "ttr_accept_count: bad sizes P = %lld, r = %lld, I = %lld", (long long)P,
               (long long)r, (long long)I);
   TTR_REQUIRE(r <= kMaxRank, TTR_E_INVALID, "ttr_accept_count: rank %lld above the limit of %d (ttr_accept_max_rank)", (long long)r,
@@ -168,14 +168,16 @@ extern "C" int ttr_accept_count(int dtype, int64_t P, int64_t r, int64_t I, cons
   TTR_REQUIRE(I <= 2147483647LL && (double)P * (double)I < 4.0e18 / 8.0, TTR_E_UNSUPPORTED, "ttr_accept_count: frontier too large");
   TTR_REQUIRE(L && fiber && C, TTR_E_INVALID, "ttr_accept_count: null pointer");
   TTR_REQUIRE(C != L && C != fiber, TTR_E_INVALID, "ttr_accept_count: C must not be an input");
-  if (dtype == TTR_F32) return count_impl<float>({P, r, I, (const double*)L, (const float*)fiber, (int64_t*)C}, (hipStream_t)stream);
-  return count_impl<double>({P, r, I, (const double*)L, (const double*)fiber, (int64_t*)C}, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {   // (L is fp64 for both dtypes)
+    using T = decltype(t);
+    return count_impl<T>({P, r, I, (const double*)L, (const T*)fiber, (int64_t*)C}, (hipStream_t)stream);
+  });
 }
 
 extern "C" int ttr_accept_expand(int dtype, int64_t P, int64_t r, int64_t I, int64_t rn, int64_t K, int64_t N, int64_t mu, int64_t S,
                                  const void* L, const void* core, const void* C, const void* childoff, const void* cnt,
                                  const void* idx, void* Lnew, void* offnew, void* cntnew, void* Xs, void* flag, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_accept_expand: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_accept_expand: bad dtype %d", dtype);
   TTR_REQUIRE(P >= 1 && r >= 1 && I >= 1 && rn >= 1 && K >= 0 && S >= 0 && N >= 1 && mu >= 0 && mu < N, TTR_E_INVALID,
               "ttr_accept_expand: bad sizes P = %lld, core [%lld, %lld, %lld], K = %lld, S = %lld, mode %lld of %lld", (long long)P,
               (long long)r, (long long)I, (long long)rn, (long long)K, (long long)S, (long long)mu, (long long)N);
@@ -188,14 +190,11 @@ extern "C" int ttr_accept_expand(int dtype, int64_t P, int64_t r, int64_t I, int
   TTR_REQUIRE(L && core && C && childoff && cnt && flag, TTR_E_INVALID, "ttr_accept_expand: null pointer");
   TTR_REQUIRE(K == 0 || (idx && offnew && cntnew), TTR_E_INVALID, "ttr_accept_expand: null pointer (slots)");
   TTR_REQUIRE(K == 0 || S == 0 || Xs, TTR_E_INVALID, "ttr_accept_expand: null pointer (Xs)");
-  if (dtype == TTR_F32) {
-    ExpandArgs<float> a{P, r, I, rn, K, N, mu, S, (const double*)L, (const float*)core, (const int64_t*)C, (const int64_t*)childoff,
-                        (const int64_t*)cnt, (const int64_t*)idx, (double*)Lnew, (int64_t*)offnew, (int64_t*)cntnew, (int64_t*)Xs,
-                        (int*)flag};
-    return expand_impl<float>(a, (hipStream_t)stream);
-  }
-  ExpandArgs<double> a{P, r, I, rn, K, N, mu, S, (const double*)L, (const double*)core, (const int64_t*)C, (const int64_t*)childoff,
-                       (const int64_t*)cnt, (const int64_t*)idx, (double*)Lnew, (int64_t*)offnew, (int64_t*)cntnew, (int64_t*)Xs,
-                       (int*)flag};
-  return expand_impl<double>(a, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {   // (L and Lnew are fp64 for both dtypes)
+    using T = decltype(t);
+    return expand_impl<T>({P, r, I, rn, K, N, mu, S, (const double*)L, (const T*)core, (const int64_t*)C, (const int64_t*)childoff,
+                           (const int64_t*)cnt, (const int64_t*)idx, (double*)Lnew, (int64_t*)offnew, (int64_t*)cntnew, (int64_t*)Xs,
+                           (int*)flag},
+                          (hipStream_t)stream);
+  });
 }

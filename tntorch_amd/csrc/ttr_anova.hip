@@ -14,7 +14,7 @@
 // The chunks' partial sums go to [S, nsplit, C C] in the caller's workspace and ttr_mode_reduce adds them in chunk order (with
 // one chunk the kernel writes Q itself): no atomics, workgroups never communicate, and the chunk length follows from (S, I)
 // alone, so the same call gives the same bits.  Every global read and write is guarded by its extent; ragged tiles are zeros.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -35,18 +35,6 @@ struct SwArgs {
   T* out;  // Q (nsplit == 1) or the partials
   int64_t chunk, nsplit;
 };
-
-bool dtype_ok(int dtype) { return dtype == TTR_F32 || dtype == TTR_F64; }
-
-// element strides of a contiguous tensor of these extents?  (the stride of an extent-1 axis is never used: anything goes)
-bool contiguous(const int64_t* shape, const int64_t* strides, int nd) {
-  int64_t want = 1;
-  for (int d = nd - 1; d >= 0; --d) {
-    if (shape[d] != 1 && strides[d] != want) return false;
-    want *= shape[d];
-  }
-  return true;
-}
 
 // slices of i per workgroup: S * nsplit workgroups aim at kSwTargetBlocks, no chunk shorter than kSwMinChunk
 int64_t sw_chunk(int64_t S, int64_t I) {
@@ -225,7 +213,7 @@ extern "C" int64_t ttr_mode_sandwich_workspace_bytes(int dtype, int64_t S, int64
   const int rc = sandwich_check(dtype, S, R, I, C);
   if (rc != TTR_OK) return rc;
   const int64_t nsplit = ceil_div(I, sw_chunk(S, I));
-  return nsplit > 1 ? align_up(S * nsplit * C * C * (dtype == TTR_F64 ? 8 : 4), 256) : 0;
+  return nsplit > 1 ? align_up(S * nsplit * C * C * elem_size(dtype), 256) : 0;
 }
 
 extern "C" int ttr_mode_sandwich(int dtype, int64_t S, int64_t R, int64_t I, int64_t C, const void* Z, const void* A,
@@ -241,10 +229,9 @@ extern "C" int ttr_mode_sandwich(int dtype, int64_t S, int64_t R, int64_t I, int
               (long long)workspace_bytes, (long long)need);
   const int64_t chunk = sw_chunk(S, I);
   const int64_t nsplit = ceil_div(I, chunk);
-  if (dtype == TTR_F32) {
-    SwArgs<float> p{S, R, I, C, (const float*)Z, (const float*)A, (const float*)w, (const float*)mu, nullptr, chunk, nsplit};
-    return sandwich_impl<float>(p, Q, workspace, (hipStream_t)stream);
-  }
-  SwArgs<double> p{S, R, I, C, (const double*)Z, (const double*)A, (const double*)w, (const double*)mu, nullptr, chunk, nsplit};
-  return sandwich_impl<double>(p, Q, workspace, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return sandwich_impl<T>({S, R, I, C, (const T*)Z, (const T*)A, (const T*)w, (const T*)mu, nullptr, chunk, nsplit}, Q, workspace,
+                            (hipStream_t)stream);
+  });
 }

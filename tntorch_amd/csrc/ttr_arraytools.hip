@@ -22,7 +22,7 @@
 // to another, nothing is atomic, there is no scratch: tiling, chunks and with them the order of every sum follow from (R, I, C)
 // and the dtype alone.  Both dtypes accumulate in fp64 registers and round once, at the store.  Rows outside a wave's chunk and
 // packs outside the tile are never loaded or stored; every extent and stride comes from validated host arguments.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -33,11 +33,6 @@ constexpr int kUnroll = 4;             // steps of g rows in flight per wave
 constexpr int64_t kMaxBlocks = 2048;   // 256 CUs x 8 blocks; the rest of the items is walked with a grid stride
 constexpr int64_t kEnoughItems = 1024; // one wave per SIMD of the device: from here on an item is one wave's
 constexpr int64_t kSplitItems = 256;   // the split kernels: one workgroup per CU; below it the tiles are narrowed
-
-template <typename T, int P>
-struct alignas(sizeof(T) * P) Pack {
-  T v[P];
-};
 
 template <typename T>
 struct ArrArgs {
@@ -225,20 +220,6 @@ __global__ __launch_bounds__(NW == 1 ? kThreads : NW * kWave) void mode_reduce_k
   }
 }
 
-bool dtype_ok(int dtype) { return dtype == TTR_F32 || dtype == TTR_F64; }
-
-// element strides of a contiguous tensor of these extents?  (the stride of an extent-1 axis is never used: anything goes)
-bool contiguous(const int64_t* shape, const int64_t* strides, int nd) {
-  int64_t want = 1;
-  for (int d = nd - 1; d >= 0; --d) {
-    if (shape[d] != 1 && strides[d] != want) return false;
-    want *= shape[d];
-  }
-  return true;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // tiling and chunks of a core for packs of P elements; true: the waves of a workgroup split I
 template <typename T>
 bool plan(ArrArgs<T>& p, int P) {
@@ -311,20 +292,6 @@ int reduce_impl(ArrArgs<T> p, hipStream_t stream) {
   return TTR_OK;
 }
 
-// the checks the two entries share: sizes, pointers, the contiguous X
-int arr_check(const char* who, int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, const void* Y,
-              const int64_t* y_strides) {
-  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
-  TTR_REQUIRE(R >= 1 && I >= 1 && C >= 1, TTR_E_INVALID, "%s: bad sizes R = %lld, I = %lld, C = %lld", who, (long long)R, (long long)I,
-              (long long)C);
-  TTR_REQUIRE(X && x_strides && Y && y_strides, TTR_E_INVALID, "%s: null pointer", who);
-  TTR_REQUIRE(X != Y, TTR_E_INVALID, "%s: X and Y must be different buffers", who);
-  const int64_t xs[3] = {R, I, C};
-  TTR_REQUIRE(contiguous(xs, x_strides, 3), TTR_E_UNSUPPORTED, "%s: X must be contiguous", who);
-  TTR_REQUIRE((double)R * (double)I * (double)C < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "%s: core too large", who);
-  return TTR_OK;
-}
-
 }  // namespace
 
 }  // namespace ttr
@@ -333,25 +300,20 @@ using namespace ttr;
 
 extern "C" int ttr_mode_scan(int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, void* Y,
                              const int64_t* y_strides, void* stream) {
-  const int rc = arr_check("ttr_mode_scan", dtype, R, I, C, X, x_strides, Y, y_strides);
+  int rc = core_check("ttr_mode_scan", dtype, R, I, C, X, x_strides, Y, "Y", y_strides != nullptr);
   if (rc != TTR_OK) return rc;
-  // Y [R, I, C] with element strides (sr, si, 1), rows and slabs that do not overlap; the stride of an extent-1 axis is free
-  const int64_t si = I > 1 ? y_strides[1] : C;
-  const int64_t sr = R > 1 ? y_strides[0] : I * si;
-  TTR_REQUIRE((C == 1 || y_strides[2] == 1) && si >= C && sr >= I * si, TTR_E_UNSUPPORTED,
-              "ttr_mode_scan: Y needs element strides (sr, si, 1) with si >= C and sr >= I si");
-  TTR_REQUIRE((double)R * (double)sr < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "ttr_mode_scan: Y too large");
-  if (dtype == TTR_F32) {
-    ArrArgs<float> p{R, I, C, (const float*)X, nullptr, (float*)Y, sr, si, 1.0};
-    return scan_impl<float>(p, (hipStream_t)stream);
-  }
-  ArrArgs<double> p{R, I, C, (const double*)X, nullptr, (double*)Y, sr, si, 1.0};
-  return scan_impl<double>(p, (hipStream_t)stream);
+  int64_t sr, si;
+  rc = strided_y_check("ttr_mode_scan", R, I, C, y_strides, &sr, &si);
+  if (rc != TTR_OK) return rc;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return scan_impl<T>({R, I, C, (const T*)X, nullptr, (T*)Y, sr, si, 1.0}, (hipStream_t)stream);
+  });
 }
 
 extern "C" int ttr_mode_reduce(int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, const void* w,
                                double scale, void* Y, const int64_t* y_strides, void* stream) {
-  const int rc = arr_check("ttr_mode_reduce", dtype, R, I, C, X, x_strides, Y, y_strides);
+  const int rc = core_check("ttr_mode_reduce", dtype, R, I, C, X, x_strides, Y, "Y", y_strides != nullptr);
   if (rc != TTR_OK) return rc;
   TTR_REQUIRE(w != Y, TTR_E_INVALID, "ttr_mode_reduce: w and Y must be different buffers");
   // Y [R, C] with element strides (sr, 1) and rows that do not overlap; the stride of an extent-1 axis is free
@@ -359,10 +321,8 @@ extern "C" int ttr_mode_reduce(int dtype, int64_t R, int64_t I, int64_t C, const
   TTR_REQUIRE((C == 1 || y_strides[1] == 1) && sr >= C, TTR_E_UNSUPPORTED,
               "ttr_mode_reduce: Y needs element strides (sr, 1) with sr >= C");
   TTR_REQUIRE((double)R * (double)sr < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "ttr_mode_reduce: Y too large");
-  if (dtype == TTR_F32) {
-    ArrArgs<float> p{R, I, C, (const float*)X, (const float*)w, (float*)Y, sr, 0, scale};
-    return reduce_impl<float>(p, (hipStream_t)stream);
-  }
-  ArrArgs<double> p{R, I, C, (const double*)X, (const double*)w, (double*)Y, sr, 0, scale};
-  return reduce_impl<double>(p, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return reduce_impl<T>({R, I, C, (const T*)X, (const T*)w, (T*)Y, sr, 0, scale}, (hipStream_t)stream);
+  });
 }

@@ -17,7 +17,7 @@
 //
 // Round 2 ran this loop on the host (index_select x 3, stack, 3 GEMM launches + permute copies per round, one .item() per
 // sweep: ~320 launches per n = 256 bond, 2 % of C3's roofline).
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 

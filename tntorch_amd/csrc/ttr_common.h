@@ -106,6 +106,17 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// Block-wide sum of doubles (256 threads), result in every thread.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();  // `red` may still be read from a previous call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0;
+  for (int w = 0; w < kThreads / kWave; ++w) s += red[w];
+  return s;
+}
+
 // Sum over the 64 lanes, result in every lane.  Row (16-lane) sums with four DPP steps -- VALU only, no
 // LDS crossbar -- then the four row sums are combined through SGPRs (readlane).
 template <int CTRL>
@@ -250,6 +261,12 @@ __device__ __forceinline__ int rank_rule(const T* s, int n_live, int n_full, int
   if (rk < 1) rk = 1;
   return (int)rk;
 }
+
+// V consecutive elements that move as one load / store of sizeof(T) * V bytes where the address is aligned to that
+template <typename T, int V>
+struct alignas(sizeof(T) * V) Pack {
+  T v[V];
+};
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }

@@ -9,7 +9,7 @@
 //   ttr_spd_solve    sums the tasks of each slice on load and solves G x = h by Cholesky, one workgroup per slice, and writes x
 //                    straight into the new core; a slice whose pivot falls to K eps max(diag G) or below is flagged and left to
 //                    the minimum-norm fallback (ttr_eigh_trunc + ttr_gemm + ttr_pinv_finish).
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 namespace {
@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(kThreads) pinv_finish_kernel(int K, const T* _
 }
 
 int64_t stage_rows(int dtype, int64_t r0, int64_t r1) {  // samples staged per pass of ttr_als_normal: a multiple of 4, <= 256
-  const int64_t es = dtype == TTR_F32 ? 4 : 8;
+  const int64_t es = elem_size(dtype);
   int64_t S = kStageBytes / ((r0 + r1 + 1) * es + 8);
   S = S > 256 ? 256 : S;
   return S & ~(int64_t)3;
@@ -278,7 +278,7 @@ extern "C" int64_t ttr_als_normal_groups(int64_t r0, int64_t r1) {
 extern "C" int ttr_als_normal(int dtype, int64_t ntasks, int64_t r0, int64_t r1, const void* L, int64_t ldl, const void* R,
                               int64_t ldr, const void* w, const void* y, const void* perm, const void* task_begin,
                               const void* task_end, void* Gp, void* hp, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_als_normal: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_als_normal: bad dtype %d", dtype);
   TTR_REQUIRE(ntasks >= 0 && r0 >= 1 && r1 >= 1 && ldl >= r0 && ldr >= r1, TTR_E_INVALID, "ttr_als_normal: bad sizes");
   TTR_REQUIRE(r0 * r1 <= kMaxK, TTR_E_UNSUPPORTED, "ttr_als_normal: r0 * r1 = %lld above %lld", (long long)(r0 * r1),
               (long long)kMaxK);
@@ -287,18 +287,16 @@ extern "C" int ttr_als_normal(int dtype, int64_t ntasks, int64_t r0, int64_t r1,
   TTR_REQUIRE(L && R && y && perm && task_begin && task_end && Gp && hp, TTR_E_INVALID, "ttr_als_normal: NULL argument");
   const int64_t S = stage_rows(dtype, r0, r1);
   TTR_REQUIRE(S >= 4, TTR_E_UNSUPPORTED, "ttr_als_normal: ranks too large to stage");
-  const int64_t es = dtype == TTR_F32 ? 4 : 8;
+  const int64_t es = elem_size(dtype);
   const size_t lds = (size_t)(S * (r0 + r1 + 1) * es + S * 8);
   const dim3 grid((unsigned)ntasks, (unsigned)ttr_als_normal_groups(r0, r1));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TTR_F32)
-    hipLaunchKernelGGL(als_normal_kernel<float>, grid, dim3(kThreads), lds, s, (int)r0, (int)r1, (int)S, (const float*)L, ldl,
-                       (const float*)R, ldr, (const float*)w, (const float*)y, (const int64_t*)perm, (const int64_t*)task_begin,
-                       (const int64_t*)task_end, (float*)Gp, (float*)hp);
-  else
-    hipLaunchKernelGGL(als_normal_kernel<double>, grid, dim3(kThreads), lds, s, (int)r0, (int)r1, (int)S, (const double*)L, ldl,
-                       (const double*)R, ldr, (const double*)w, (const double*)y, (const int64_t*)perm,
-                       (const int64_t*)task_begin, (const int64_t*)task_end, (double*)Gp, (double*)hp);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(als_normal_kernel<T>, grid, dim3(kThreads), lds, s, (int)r0, (int)r1, (int)S, (const T*)L, ldl, (const T*)R, ldr,
+                       (const T*)w, (const T*)y, (const int64_t*)perm, (const int64_t*)task_begin, (const int64_t*)task_end, (T*)Gp,
+                       (T*)hp);
+  });
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }
@@ -322,7 +320,7 @@ static int spd_solve_typed(int64_t n_items, int64_t K, const void* Gp, const voi
 extern "C" int ttr_spd_solve(int dtype, int64_t n_items, int64_t K, const void* Gp, const void* hp, const void* part_off,
                              int64_t part_base, void* X, int64_t inner, int64_t s_item, int64_t s_a, int64_t s_b, void* Gsum,
                              void* hsum, void* status, const void* counts, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_spd_solve: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_spd_solve: bad dtype %d", dtype);
   TTR_REQUIRE(n_items >= 0 && K >= 1 && inner >= 1, TTR_E_INVALID, "ttr_spd_solve: bad sizes");
   TTR_REQUIRE(K <= kMaxK, TTR_E_UNSUPPORTED, "ttr_spd_solve: K = %lld above %lld", (long long)K, (long long)kMaxK);
   TTR_REQUIRE(n_items < ((int64_t)1 << 31), TTR_E_UNSUPPORTED, "ttr_spd_solve: too many items");
@@ -330,27 +328,26 @@ extern "C" int ttr_spd_solve(int dtype, int64_t n_items, int64_t K, const void* 
   TTR_REQUIRE(Gp && hp && part_off && X && Gsum && hsum && status, TTR_E_INVALID, "ttr_spd_solve: NULL argument");
   const XOut xo{inner, s_item, s_a, s_b};
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TTR_F32)
-    return spd_solve_typed<float>(n_items, K, Gp, hp, part_off, part_base, X, xo, Gsum, hsum, status, counts, s);
-  return spd_solve_typed<double>(n_items, K, Gp, hp, part_off, part_base, X, xo, Gsum, hsum, status, counts, s);
+  return by_dtype(dtype, [&](auto t) {
+    return spd_solve_typed<decltype(t)>(n_items, K, Gp, hp, part_off, part_base, X, xo, Gsum, hsum, status, counts, s);
+  });
 }
 
 extern "C" int ttr_pinv_finish(int dtype, int64_t n_items, int64_t K, const void* V, const void* sigma, const void* t,
                                const void* status, void* X, int64_t inner, int64_t s_item, int64_t s_a, int64_t s_b,
                                void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_pinv_finish: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_pinv_finish: bad dtype %d", dtype);
   TTR_REQUIRE(n_items >= 0 && K >= 1 && inner >= 1, TTR_E_INVALID, "ttr_pinv_finish: bad sizes");
   TTR_REQUIRE(K <= kMaxK, TTR_E_UNSUPPORTED, "ttr_pinv_finish: K = %lld above %lld", (long long)K, (long long)kMaxK);
   if (n_items == 0) return TTR_OK;
   TTR_REQUIRE(V && sigma && t && status && X, TTR_E_INVALID, "ttr_pinv_finish: NULL argument");
   const XOut xo{inner, s_item, s_a, s_b};
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TTR_F32)
-    hipLaunchKernelGGL(pinv_finish_kernel<float>, dim3((unsigned)n_items), dim3(kThreads), 0, s, (int)K, (const float*)V,
-                       (const float*)sigma, (const float*)t, (const int32_t*)status, (float*)X, xo);
-  else
-    hipLaunchKernelGGL(pinv_finish_kernel<double>, dim3((unsigned)n_items), dim3(kThreads), 0, s, (int)K, (const double*)V,
-                       (const double*)sigma, (const double*)t, (const int32_t*)status, (double*)X, xo);
+  by_dtype(dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(pinv_finish_kernel<T>, dim3((unsigned)n_items), dim3(kThreads), 0, s, (int)K, (const T*)V, (const T*)sigma,
+                       (const T*)t, (const int32_t*)status, (T*)X, xo);
+  });
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }

@@ -16,7 +16,7 @@
 //
 // Every index comes from validated host arguments; global offsets are 64-bit.  Loads outside the tile's columns, the chunk or
 // the long mode are replaced by zeros, stores outside [0, K) x [0, R2 S2) are skipped.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -25,11 +25,6 @@ namespace {
 constexpr int kMaxTaps = 32;  // terms of the sum staged in LDS at once; above it the sum is chunked
 constexpr int kTileC = 64;    // output columns per workgroup
 constexpr int kKPT = 4;       // consecutive k per thread
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
 
 template <typename T>
 struct ConvArgs {
@@ -136,7 +131,7 @@ int launch(ConvArgs<T> p, hipStream_t stream) {
 template <typename T>
 int convolve_impl(ConvArgs<T> p, hipStream_t stream) {
   constexpr int VW = 16 / (int)sizeof(T);
-  const bool wide = (p.R2 * p.S2) % VW == 0 && ((uintptr_t)p.out & 15) == 0;
+  const bool wide = (p.R2 * p.S2) % VW == 0 && aligned16(p.out);
   return wide ? launch<T, VW>(p, stream) : launch<T, 1>(p, stream);
 }
 
@@ -150,7 +145,7 @@ extern "C" int ttr_core_convolve_max_taps(void) { return kMaxTaps; }
 
 extern "C" int ttr_core_convolve(int dtype, int64_t R1, int64_t I, int64_t R2, int64_t S1, int64_t J, int64_t S2, int64_t lo,
                                  int64_t K, const void* a, const void* c, void* out, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_core_convolve: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_core_convolve: bad dtype %d", dtype);
   TTR_REQUIRE(R1 >= 1 && I >= 1 && R2 >= 1 && S1 >= 1 && J >= 1 && S2 >= 1 && K >= 1, TTR_E_INVALID,
               "ttr_core_convolve: bad sizes [%lld, %lld, %lld] x [%lld, %lld, %lld], K = %lld", (long long)R1, (long long)I,
               (long long)R2, (long long)S1, (long long)J, (long long)S2, (long long)K);
@@ -164,10 +159,8 @@ extern "C" int ttr_core_convolve(int dtype, int64_t R1, int64_t I, int64_t R2, i
   TTR_REQUIRE(out != a && out != c, TTR_E_INVALID, "ttr_core_convolve: out must not be an input");
   TTR_REQUIRE(R1 * S1 <= lim && R2 * S2 <= lim && (double)R1 * (double)S1 * (double)K * (double)R2 * (double)S2 < 9.0e18 / 64.0,
               TTR_E_UNSUPPORTED, "ttr_core_convolve: result too large");
-  if (dtype == TTR_F32) {
-    ConvArgs<float> p{R1, I, R2, S1, J, S2, lo, K, 0, 0, (const float*)a, (const float*)c, (float*)out};
-    return convolve_impl<float>(p, (hipStream_t)stream);
-  }
-  ConvArgs<double> p{R1, I, R2, S1, J, S2, lo, K, 0, 0, (const double*)a, (const double*)c, (double*)out};
-  return convolve_impl<double>(p, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return convolve_impl<T>({R1, I, R2, S1, J, S2, lo, K, 0, 0, (const T*)a, (const T*)c, (T*)out}, (hipStream_t)stream);
+  });
 }

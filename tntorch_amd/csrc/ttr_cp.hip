@@ -3,7 +3,6 @@
 // partially contracted tensor of a fused MTTKRP into the next one, and the Hadamard product of the R x R
 // Gram matrices.  HBM-streaming kernels: T is read exactly once, coalesced; no Khatri-Rao matrix and no
 // permuted unfolding copy is ever materialised.
-#include "ttr_common.h"
 #include "detail/ttr_internal.h"  // declares the dispatchers defined below
 
 namespace ttr {

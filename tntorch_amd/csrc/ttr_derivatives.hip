@@ -14,7 +14,7 @@
 // exactly (S^3 = 0 for I = 3, S^2 = 0 for I = 2: the rows of the lower power coincide) fp32 input gives the exact zero that the
 // fp64 pass gives instead of cancellation noise at eps times the lower power.  Rows outside [0, I) are never read (periodic:
 // wrapped), and every extent and stride comes from validated host arguments.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -22,11 +22,6 @@ namespace {
 
 constexpr int kDiffMaxOrder = 4;   // passes fused into one launch: 2 * 4 + 1 rows of V values in registers
 constexpr int64_t kMaxBlocks = 2048;  // 256 CUs x 8 blocks; the rest of the items is walked with a grid stride
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
 
 template <typename T>
 struct DiffArgs {
@@ -153,24 +148,10 @@ __global__ __launch_bounds__(kThreads) void laplace_core_kernel(DiffArgs<T> p) {
   }
 }
 
-bool dtype_ok(int dtype) { return dtype == TTR_F32 || dtype == TTR_F64; }
-
-// element strides of a contiguous tensor of these extents?  (the stride of an extent-1 axis is never used: anything goes)
-bool contiguous(const int64_t* shape, const int64_t* strides, int nd) {
-  int64_t want = 1;
-  for (int d = nd - 1; d >= 0; --d) {
-    if (shape[d] != 1 && strides[d] != want) return false;
-    want *= shape[d];
-  }
-  return true;
-}
-
 unsigned grid_for(int64_t total) {
   const int64_t blocks = ceil_div(total, kThreads);
   return (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <typename T, int V, bool PER>
 void mode_diff_launch_o(const DiffArgs<T>& p, int order, hipStream_t stream) {
@@ -218,19 +199,6 @@ int laplace_core_impl(DiffArgs<T> p, int periodic, hipStream_t stream) {
   return TTR_OK;
 }
 
-// the checks the two entries share: sizes, pointers, the contiguous X
-int diff_check(const char* who, int dtype, int64_t R, int64_t I, int64_t C, const void* X, const int64_t* x_strides, const void* out) {
-  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
-  TTR_REQUIRE(R >= 1 && I >= 1 && C >= 1, TTR_E_INVALID, "%s: bad sizes R = %lld, I = %lld, C = %lld", who, (long long)R, (long long)I,
-              (long long)C);
-  TTR_REQUIRE(X && x_strides && out, TTR_E_INVALID, "%s: null pointer", who);
-  TTR_REQUIRE(X != out, TTR_E_INVALID, "%s: X and the output must be different buffers", who);
-  const int64_t xs[3] = {R, I, C};
-  TTR_REQUIRE(contiguous(xs, x_strides, 3), TTR_E_UNSUPPORTED, "%s: X must be contiguous", who);
-  TTR_REQUIRE((double)R * (double)I * (double)C < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "%s: core too large", who);
-  return TTR_OK;
-}
-
 }  // namespace
 
 }  // namespace ttr
@@ -241,35 +209,28 @@ extern "C" int ttr_mode_diff_max_order(void) { return kDiffMaxOrder; }
 
 extern "C" int ttr_mode_diff(int dtype, int64_t R, int64_t I, int64_t C, int order, int periodic, double inv_step, const void* X,
                              const int64_t* x_strides, void* Y, const int64_t* y_strides, void* stream) {
-  const int rc = diff_check("ttr_mode_diff", dtype, R, I, C, X, x_strides, Y);
+  int rc = core_check("ttr_mode_diff", dtype, R, I, C, X, x_strides, Y, "the output");
   if (rc != TTR_OK) return rc;
   TTR_REQUIRE(y_strides, TTR_E_INVALID, "ttr_mode_diff: null pointer");
   TTR_REQUIRE(order >= 1, TTR_E_INVALID, "ttr_mode_diff: order %d < 1", order);
   TTR_REQUIRE(order <= kDiffMaxOrder, TTR_E_UNSUPPORTED, "ttr_mode_diff: order %d above the fused limit %d (chain calls)", order,
               kDiffMaxOrder);
-  // Y [R, I, C] with element strides (sr, si, 1), rows and slabs that do not overlap; the stride of an extent-1 axis is free
-  const int64_t si = I > 1 ? y_strides[1] : C;
-  const int64_t sr = R > 1 ? y_strides[0] : I * si;
-  TTR_REQUIRE((C == 1 || y_strides[2] == 1) && si >= C && sr >= I * si, TTR_E_UNSUPPORTED,
-              "ttr_mode_diff: Y needs element strides (sr, si, 1) with si >= C and sr >= I si");
-  TTR_REQUIRE((double)R * (double)sr < 9.0e18 / 64.0, TTR_E_UNSUPPORTED, "ttr_mode_diff: Y too large");
-  if (dtype == TTR_F32) {
-    DiffArgs<float> p{R, I, C, (const float*)X, (float*)Y, sr, si, 0, inv_step};
-    return mode_diff_impl<float>(p, order, periodic != 0, (hipStream_t)stream);
-  }
-  DiffArgs<double> p{R, I, C, (const double*)X, (double*)Y, sr, si, 0, inv_step};
-  return mode_diff_impl<double>(p, order, periodic != 0, (hipStream_t)stream);
+  int64_t sr, si;
+  rc = strided_y_check("ttr_mode_diff", R, I, C, y_strides, &sr, &si);
+  if (rc != TTR_OK) return rc;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return mode_diff_impl<T>({R, I, C, (const T*)X, (T*)Y, sr, si, 0, inv_step}, order, periodic != 0, (hipStream_t)stream);
+  });
 }
 
 extern "C" int ttr_laplace_core(int dtype, int64_t R, int64_t I, int64_t C, int pos, int periodic, double inv_step, const void* X,
                                 const int64_t* x_strides, void* out, void* stream) {
-  const int rc = diff_check("ttr_laplace_core", dtype, R, I, C, X, x_strides, out);
+  const int rc = core_check("ttr_laplace_core", dtype, R, I, C, X, x_strides, out, "the output");
   if (rc != TTR_OK) return rc;
   TTR_REQUIRE(pos >= 0 && pos <= 2, TTR_E_INVALID, "ttr_laplace_core: pos %d is none of 0 (first), 1 (middle), 2 (last)", pos);
-  if (dtype == TTR_F32) {
-    DiffArgs<float> p{R, I, C, (const float*)X, (float*)out, 0, 0, pos, inv_step};
-    return laplace_core_impl<float>(p, periodic != 0, (hipStream_t)stream);
-  }
-  DiffArgs<double> p{R, I, C, (const double*)X, (double*)out, 0, 0, pos, inv_step};
-  return laplace_core_impl<double>(p, periodic != 0, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return laplace_core_impl<T>({R, I, C, (const T*)X, (T*)out, 0, 0, pos, inv_step}, periodic != 0, (hipStream_t)stream);
+  });
 }

@@ -25,7 +25,7 @@
 // tail-energy scan (accumulated in double like torch.cumsum on CPU), rank selection.
 #include <type_traits>
 
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 

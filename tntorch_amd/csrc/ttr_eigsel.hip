@@ -19,7 +19,6 @@
 // The host shim orthonormalises Z with the TSQR kernel between the last two (close eigenvalues leave the twisted vectors
 // only nearly orthogonal) and checks the diagonal of that R for collapsed columns (clusters / multiple eigenvalues: the caller
 // falls back to the block-Jacobi driver).
-#include "ttr_common.h"
 #include "detail/ttr_internal.h"  // declares the dispatchers defined below
 
 namespace ttr {

@@ -16,7 +16,7 @@
 //   mn-contiguous operand -> LDS [k][mn], leading dim 80   (fragment read: 80*k + i)
 // Optional split-K (blockIdx.y) writes partial tiles to a workspace, reduced (and
 // scaled) by a second kernel -- used for the Gram matrices of very tall unfoldings.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 

@@ -26,7 +26,7 @@
 //      updates).
 //
 // NaN values count as 0 in every argmax, so a pivot is always a valid row (nonsense in, nonsense out, never out of bounds).
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 namespace {
@@ -307,8 +307,6 @@ __global__ void __launch_bounds__(kThreads) swap_kernel(const T* __restrict__ Ci
   if (blockIdx.x == 0 && tid == 0) index[b * r + q] = p;
 }
 
-int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
-
 struct Layout {
   int64_t c0, c1, x, pos, parts, status, total;
 };
@@ -369,14 +367,14 @@ int maxvol_impl(int64_t batch, int64_t N, int64_t r, const T* A, int64_t sa, dou
 using namespace ttr;
 
 extern "C" int64_t ttr_maxvol_workspace_bytes(int dtype, int64_t N, int64_t r, int64_t batch) {
-  if ((dtype != TTR_F32 && dtype != TTR_F64) || N < 1 || r < 1 || batch < 1) return -1;
-  return layout(dtype == TTR_F32 ? 4 : 8, N, r, batch).total;
+  if (!dtype_ok(dtype) || N < 1 || r < 1 || batch < 1) return -1;
+  return layout(elem_size(dtype), N, r, batch).total;
 }
 
 extern "C" int ttr_maxvol(int dtype, int64_t batch, int64_t N, int64_t r, const void* A, int64_t stride_ab, double tol,
                           int64_t max_iters, void* index, void* C, int64_t stride_cb, void* status, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_maxvol: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_maxvol: bad dtype %d", dtype);
   TTR_REQUIRE(batch >= 1 && r >= 1 && N > r, TTR_E_INVALID, "ttr_maxvol: bad sizes (batch %lld, N %lld, r %lld; needs N > r)",
               (long long)batch, (long long)N, (long long)r);
   TTR_REQUIRE(max_iters >= 0, TTR_E_INVALID, "ttr_maxvol: max_iters %lld < 0", (long long)max_iters);
@@ -385,14 +383,14 @@ extern "C" int ttr_maxvol(int dtype, int64_t batch, int64_t N, int64_t r, const 
   TTR_REQUIRE(r <= kMaxR, TTR_E_UNSUPPORTED, "ttr_maxvol: r %lld above %lld", (long long)r, (long long)kMaxR);
   TTR_REQUIRE(batch <= 65535, TTR_E_UNSUPPORTED, "ttr_maxvol: batch %lld above 65535", (long long)batch);
   TTR_REQUIRE(N < ((int64_t)1 << 31) / kMaxR, TTR_E_UNSUPPORTED, "ttr_maxvol: N %lld too large", (long long)N);
-  const Layout L = layout(dtype == TTR_F32 ? 4 : 8, N, r, batch);
+  const Layout L = layout(elem_size(dtype), N, r, batch);
   TTR_REQUIRE(workspace && workspace_bytes >= L.total, TTR_E_WORKSPACE, "ttr_maxvol: workspace %lld < %lld bytes",
               (long long)workspace_bytes, (long long)L.total);
   hipStream_t s = (hipStream_t)stream;
   if (tol < 1.0) tol = 1.0;
-  if (dtype == TTR_F32)
-    return maxvol_impl<float>(batch, N, r, (const float*)A, stride_ab, tol, max_iters, (int64_t*)index, (float*)C, stride_cb,
-                              (int32_t*)status, (char*)workspace, L, s);
-  return maxvol_impl<double>(batch, N, r, (const double*)A, stride_ab, tol, max_iters, (int64_t*)index, (double*)C, stride_cb,
-                             (int32_t*)status, (char*)workspace, L, s);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return maxvol_impl<T>(batch, N, r, (const T*)A, stride_ab, tol, max_iters, (int64_t*)index, (T*)C, stride_cb, (int32_t*)status,
+                          (char*)workspace, L, s);
+  });
 }

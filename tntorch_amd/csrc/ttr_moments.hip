@@ -10,7 +10,7 @@
 // the LDS image of either operand is [k][mn]: in every use here the mn index of at least one operand is the unit-stride axis,
 // and consecutive threads stage consecutive mn.  Every global read and write is guarded by its extent (ragged tiles are zero
 // filled), and every extent and stride comes from validated host arguments.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -159,18 +159,6 @@ int contract_launch(ConArgs<T> p, int64_t batch, hipStream_t stream, const char*
   return TTR_OK;
 }
 
-bool dtype_ok(int dtype) { return dtype == TTR_F32 || dtype == TTR_F64; }
-
-// element strides of a contiguous tensor of these extents?  (the stride of an extent-1 axis is never used: anything goes)
-bool contiguous(const int64_t* shape, const int64_t* strides, int nd) {
-  int64_t want = 1;
-  for (int d = nd - 1; d >= 0; --d) {
-    if (shape[d] != 1 && strides[d] != want) return false;
-    want *= shape[d];
-  }
-  return true;
-}
-
 // out[p A + a, s, q C + c] = sum_k x[p, k, q] G[a, k, s, c]: batch (p, s), rows q, columns (a, c)
 template <typename T>
 int core_matvec_impl(int64_t P, int64_t K, int64_t Q, int64_t A, int64_t S, int64_t C, const void* x, const void* G, void* out,
@@ -271,15 +259,14 @@ extern "C" int ttr_core_matvec(int dtype, int64_t P, int64_t K, int64_t Q, int64
   TTR_REQUIRE((double)P * (double)A * (double)S * (double)Q * (double)C < lim && (double)A * (double)K * (double)S * (double)C < lim &&
                   (double)P * (double)K * (double)Q < lim && A <= 2147483647LL / C && P <= 2147483647LL / S,
               TTR_E_UNSUPPORTED, "ttr_core_matvec: core too large");
-  if (dtype == TTR_F32) return core_matvec_impl<float>(P, K, Q, A, S, C, x, G, out, (hipStream_t)stream);
-  return core_matvec_impl<double>(P, K, Q, A, S, C, x, G, out, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) { return core_matvec_impl<decltype(t)>(P, K, Q, A, S, C, x, G, out, (hipStream_t)stream); });
 }
 
 extern "C" int64_t ttr_hsum_step_workspace_bytes(int dtype, int64_t K, int64_t I, const int64_t* r_in, const int64_t* r_out) {
   const int rc = hsum_check(dtype, K, I, r_in, r_out);
   if (rc != TTR_OK) return rc;
   const int64_t mx = hsum_max_elems(K, I, r_in, r_out);
-  const int64_t elem = dtype == TTR_F64 ? 8 : 4;
+  const int64_t elem = elem_size(dtype);
   TTR_REQUIRE(mx >= 0 && mx <= kHsumMaxScratch / (2 * elem), TTR_E_UNSUPPORTED,
               "ttr_hsum_step: the intermediates of these ranks need more than %lld bytes of scratch", (long long)kHsumMaxScratch);
   return 2 * align_up(mx * elem, 256);
@@ -298,6 +285,5 @@ extern "C" int ttr_hsum_step(int dtype, int64_t K, int64_t I, const int64_t* r_i
   }
   TTR_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), TTR_E_WORKSPACE, "ttr_hsum_step: workspace %lld < %lld bytes",
               (long long)workspace_bytes, (long long)need);
-  if (dtype == TTR_F32) return hsum_step_impl<float>(K, I, r_in, r_out, W, cores, Wout, workspace, (hipStream_t)stream);
-  return hsum_step_impl<double>(K, I, r_in, r_out, W, cores, Wout, workspace, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) { return hsum_step_impl<decltype(t)>(K, I, r_in, r_out, W, cores, Wout, workspace, (hipStream_t)stream); });
 }

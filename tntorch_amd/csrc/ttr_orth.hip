@@ -15,18 +15,6 @@
 
 namespace ttr {
 
-// Block-wide sum of doubles (256 threads), result in every thread.  (ttr_vec.hip carries the same ten lines: see the follow-up
-// in detail/ttr_internal.h)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();  // `red` may still be read from a previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0;
-  for (int w = 0; w < kThreads / kWave; ++w) s += red[w];
-  return s;
-}
-
 // One workgroup per batch item; see ttr_orth_fixup in the header.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void orth_fixup_kernel(int r, int64_t n, T* __restrict__ X, int64_t vs, int64_t es,
@@ -771,7 +759,7 @@ extern "C" {
 
 int64_t ttr_orth_fixup_workspace_bytes(int dtype, int64_t r, int64_t n, int64_t batch, int64_t elem_stride) {
   if (!dtype_ok(dtype) || !orth_split_ok(r, n, batch, elem_stride)) return 0;
-  return orth_split_layout(r, n, batch, dtype == TTR_F32 ? 4 : 8, g_orth_rounds).total;
+  return orth_split_layout(r, n, batch, elem_size(dtype), g_orth_rounds).total;
 }
 
 int ttr_orth_fixup(int dtype, int64_t r, int64_t n, int64_t batch, void* X, int64_t vec_stride, int64_t elem_stride,
@@ -785,7 +773,7 @@ int ttr_orth_fixup(int dtype, int64_t r, int64_t n, int64_t batch, void* X, int6
   const int32_t* of_skip = nullptr;   // (set when the three-launch rounds ran first: what they left over goes to the single launch)
   int of_round0 = 0;
   if (workspace && orth_split_ok(r, n, batch, elem_stride) &&
-      workspace_bytes >= orth_split_layout(r, n, batch, dtype == TTR_F32 ? 4 : 8, g_orth_rounds).total) {
+      workspace_bytes >= orth_split_layout(r, n, batch, elem_size(dtype), g_orth_rounds).total) {
     const int rc = dtype == TTR_F32
                        ? orth_split_run<float>(r, n, batch, (float*)X, vec_stride, strideX, (const float*)sigma, stride_sigma, dead_rel,
                                                rank_dev, (char*)workspace, s)
@@ -794,13 +782,13 @@ int ttr_orth_fixup(int dtype, int64_t r, int64_t n, int64_t batch, void* X, int6
     if (rc != TTR_OK) return rc;
     of_round0 = g_orth_rounds < kOrthSplitRounds ? g_orth_rounds : kOrthSplitRounds;
     if (of_round0 >= g_orth_rounds) return TTR_OK;
-    of_skip = (const int32_t*)((char*)workspace + orth_split_layout(r, n, batch, dtype == TTR_F32 ? 4 : 8, g_orth_rounds).off_skip) +
+    of_skip = (const int32_t*)((char*)workspace + orth_split_layout(r, n, batch, elem_size(dtype), g_orth_rounds).off_skip) +
               (int64_t)of_round0 * batch;
   }
   ProfScope prof(TTR_PROF_MISC, s);
   if (r <= 64) {  // the block variant (Gram matrix + coefficient-space Gram-Schmidt + one small product per round)
     const int cw = r <= 32 ? 256 : 128;
-    const size_t lds = orth_fixup_lds_bytes((int)r, cw, dtype == TTR_F32 ? 4 : 8);
+    const size_t lds = orth_fixup_lds_bytes((int)r, cw, elem_size(dtype));
 #define TTR_OF_LAUNCH(T_, CW_, V2_)                                                                                             \
     do {                                                                                                                          \
       auto kern = orth_fixup_block_kernel<T_, CW_, V2_>;                                                                          \

@@ -26,7 +26,7 @@
 // All arithmetic is in fp64 registers for both dtypes, rounded once at the store.  No atomics (the flag is a plain store of
 // old | 1: every writer writes the same bit), no workgroup talks to another, no scratch: tiles and with them the order of
 // every product and sum follow from (P, N, S, C) and the dtype alone.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void pce_predict_kernel(PceArgs<T> a) {
 
 int pce_check(const char* who, int dtype, int64_t P, int64_t N, int64_t S, int64_t C, const void* Z, const void* Psi,
               const void* coords, const void* out, const void* flag) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
   TTR_REQUIRE(P >= 1 && N >= 1 && S >= 1 && C >= 1, TTR_E_INVALID, "%s: bad sizes P = %lld, N = %lld, S = %lld, C = %lld", who,
               (long long)P, (long long)N, (long long)S, (long long)C);
   TTR_REQUIRE(S <= kMaxOrder, TTR_E_INVALID, "%s: S = %lld exceeds ttr_pce_max_order() = %d", who, (long long)S, kMaxOrder);
@@ -267,14 +267,11 @@ extern "C" int ttr_pce_design(int dtype, int64_t P, int64_t N, int64_t S, int64_
   if (rc != TTR_OK) return rc;
   TTR_REQUIRE(ldm >= C, TTR_E_INVALID, "ttr_pce_design: ldm = %lld < C = %lld", (long long)ldm, (long long)C);
   TTR_REQUIRE((double)P * (double)ldm < 9.0e18 / 64.0, TTR_E_INVALID, "ttr_pce_design: M too large");
-  if (dtype == TTR_F32) {
-    PceArgs<float> a{P, C, (int)N, (int)S, (const float*)Z, sz0, sz1, (const float*)Psi, (const int64_t*)coords, nullptr, (float*)M, ldm,
-                     (int*)flag};
-    return design_impl<float>(a, (hipStream_t)stream);
-  }
-  PceArgs<double> a{P, C, (int)N, (int)S, (const double*)Z, sz0, sz1, (const double*)Psi, (const int64_t*)coords, nullptr, (double*)M, ldm,
-                    (int*)flag};
-  return design_impl<double>(a, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return design_impl<T>({P, C, (int)N, (int)S, (const T*)Z, sz0, sz1, (const T*)Psi, (const int64_t*)coords, nullptr, (T*)M, ldm, (int*)flag},
+                          (hipStream_t)stream);
+  });
 }
 
 extern "C" int ttr_pce_predict(int dtype, int64_t P, int64_t N, int64_t S, int64_t C, const void* Z, int64_t sz0, int64_t sz1,
@@ -282,12 +279,10 @@ extern "C" int ttr_pce_predict(int dtype, int64_t P, int64_t N, int64_t S, int64
   const int rc = pce_check("ttr_pce_predict", dtype, P, N, S, C, Z, Psi, coords, y, flag);
   if (rc != TTR_OK) return rc;
   TTR_REQUIRE(coef, TTR_E_INVALID, "ttr_pce_predict: null pointer");
-  if (dtype == TTR_F32) {
-    PceArgs<float> a{P, C, (int)N, (int)S, (const float*)Z, sz0, sz1, (const float*)Psi, (const int64_t*)coords, (const float*)coef, (float*)y,
-                     0, (int*)flag};
-    return predict_impl<float>(a, (hipStream_t)stream);
-  }
-  PceArgs<double> a{P, C, (int)N, (int)S, (const double*)Z, sz0, sz1, (const double*)Psi, (const int64_t*)coords, (const double*)coef,
-                    (double*)y, 0, (int*)flag};
-  return predict_impl<double>(a, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return predict_impl<T>({P, C, (int)N, (int)S, (const T*)Z, sz0, sz1, (const T*)Psi, (const int64_t*)coords, (const T*)coef, (T*)y, 0,
+                            (int*)flag},
+                           (hipStream_t)stream);
+  });
 }

@@ -29,7 +29,7 @@
 // Householder step emits one coalesced 1 KiB store; T factors (16x16 per panel) sit next to them.
 #include <type_traits>
 
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 

@@ -15,7 +15,7 @@
 #include <chrono>
 #include <cstdlib>
 
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 namespace {
@@ -52,11 +52,11 @@ int64_t take(int64_t& off, int64_t bytes) {
 // Shapes + workspace layout.  Returns TTR_OK, or TTR_E_UNSUPPORTED (silently: no error text is needed for a capability probe,
 // but one is set for callers that go on regardless).
 int make_sweep_plan(int dtype, int64_t N, const int64_t* shapes, const int64_t* rcap, int64_t batch, int eps_mode, SweepPlan& p) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_round_tt: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_round_tt: bad dtype %d", dtype);
   TTR_REQUIRE(N >= 2 && N <= kMaxCores, TTR_E_UNSUPPORTED, "ttr_round_tt: %lld cores outside [2, %d]", (long long)N, kMaxCores);
   TTR_REQUIRE(batch >= 1 && batch <= 65535, TTR_E_UNSUPPORTED, "ttr_round_tt: batch %lld outside [1, 65535]", (long long)batch);
   TTR_REQUIRE(!eps_mode || batch == 1, TTR_E_UNSUPPORTED, "ttr_round_tt: the eps-mode sweep rounds ONE train (tensor.py:2039-2051)");
-  p.dt = dtype; p.es = dtype == TTR_F64 ? 8 : 4; p.N = N; p.B = batch;
+  p.dt = dtype; p.es = elem_size(dtype); p.N = N; p.B = batch;
   const int64_t maxc = ttr_qr_max_cols(dtype);
   for (int64_t mu = 0; mu < N; ++mu) {
     p.r0[mu] = shapes[3 * mu]; p.I[mu] = shapes[3 * mu + 1]; p.r1[mu] = shapes[3 * mu + 2];

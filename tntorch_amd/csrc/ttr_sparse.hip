@@ -14,7 +14,7 @@
 //
 // Every output element is one thread's ordered sum (fma chain in ascending column / ascending mode-index order); partial matrices
 // of a split i list are summed in part order.  No floating-point atomics: results are bit-identical from run to run.
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 namespace {
@@ -44,7 +44,7 @@ GramGeom gram_geom(int dtype, int64_t r, int64_t I, int64_t nb) {
   g.nTA = (int)ceil_div(r, g.TA);
   g.nTB = g.nTA;
   g.nJ = (int)ceil_div(I, g.Jt);
-  const int64_t es = dtype == TTR_F32 ? 4 : 8, n = r * I;
+  const int64_t es = elem_size(dtype), n = r * I;
   int64_t p = ceil_div(nb > 0 ? nb : 1, I * kPartBlocks);
   p = p > 16 ? 16 : p;
   while (p > 1 && p * n * n * es > kPartBytes) --p;
@@ -413,7 +413,7 @@ extern "C" int ttr_sparse_group(int64_t nb, int64_t I, const void* blk_i, void* 
 }
 
 static int sparse_gram_check(const char* who, int dtype, int64_t r, int64_t I, int64_t nb) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "%s: bad dtype %d", who, dtype);
   TTR_REQUIRE(r >= 1 && I >= 1 && nb >= 0, TTR_E_INVALID, "%s: bad sizes", who);
   const int64_t lim = ttr_eigh_max_n(dtype);
   TTR_REQUIRE(r <= lim && I <= lim && r * I <= lim, TTR_E_UNSUPPORTED, "%s: r * I = %lld above %lld", who, (long long)(r * I),
@@ -432,7 +432,7 @@ extern "C" int64_t ttr_sparse_gram_workspace_bytes(int dtype, int64_t r, int64_t
   const int st = sparse_gram_check("ttr_sparse_gram_workspace_bytes", dtype, r, I, nb);
   if (st != TTR_OK) return st;
   const int64_t n = r * I;
-  return gram_geom(dtype, r, I, nb).parts * n * n * (dtype == TTR_F32 ? 4 : 8);
+  return gram_geom(dtype, r, I, nb).parts * n * n * elem_size(dtype);
 }
 
 template <typename T>
@@ -457,14 +457,11 @@ extern "C" int ttr_sparse_gram(int dtype, int64_t r, int64_t I, int64_t nb, int6
               "ttr_sparse_gram: NULL argument");
   const GramGeom g = gram_geom(dtype, r, I, nb);
   const int64_t n = r * I;
-  TTR_REQUIRE(workspace_bytes >= g.parts * n * n * (dtype == TTR_F32 ? 4 : 8), TTR_E_WORKSPACE,
+  TTR_REQUIRE(workspace_bytes >= g.parts * n * n * elem_size(dtype), TTR_E_WORKSPACE,
               "ttr_sparse_gram: workspace too small");
   TTR_REQUIRE((int64_t)g.nJ * g.nTA * g.nTB < ((int64_t)1 << 31), TTR_E_UNSUPPORTED, "ttr_sparse_gram: too many tiles");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TTR_F32)
-    sparse_gram_launch<float>(g, nb, C, colptr, blk_i, blkcol, ilist, iptr, V, ldv, G, ldg, workspace, s);
-  else
-    sparse_gram_launch<double>(g, nb, C, colptr, blk_i, blkcol, ilist, iptr, V, ldv, G, ldg, workspace, s);
+  by_dtype(dtype, [&](auto t) { sparse_gram_launch<decltype(t)>(g, nb, C, colptr, blk_i, blkcol, ilist, iptr, V, ldv, G, ldg, workspace, s); });
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }
@@ -472,7 +469,7 @@ extern "C" int ttr_sparse_gram(int dtype, int64_t r, int64_t I, int64_t nb, int6
 extern "C" int ttr_sparse_project(int dtype, int64_t r, int64_t I, int64_t q, int64_t nb, int64_t C, const void* colptr,
                                   const void* blk_i, const void* V, int64_t ldv, const void* U, int64_t su_row, int64_t su_col,
                                   void* W, int64_t ldw, void* stream) {
-  TTR_REQUIRE(dtype == TTR_F32 || dtype == TTR_F64, TTR_E_INVALID, "ttr_sparse_project: bad dtype %d", dtype);
+  TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_sparse_project: bad dtype %d", dtype);
   TTR_REQUIRE(r >= 1 && I >= 1 && q >= 1 && nb >= 0 && C >= 0 && C <= nb && ldv >= r && ldw >= q, TTR_E_INVALID,
               "ttr_sparse_project: bad sizes");
   const int64_t lim = ttr_eigh_max_n(dtype);
@@ -484,14 +481,11 @@ extern "C" int ttr_sparse_project(int dtype, int64_t r, int64_t I, int64_t q, in
   const int64_t qq = q < kThreads ? q : kThreads, cpw = kThreads / qq;
   const dim3 grid((unsigned)ceil_div(C, cpw));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TTR_F32)
-    hipLaunchKernelGGL(sparse_project_kernel<float>, grid, dim3(kThreads), 0, s, (int)r, (int)I, (int)q, nb, C,
-                       (const int32_t*)colptr, (const int32_t*)blk_i, (const float*)V, ldv, (const float*)U, su_row, su_col,
-                       (float*)W, ldw);
-  else
-    hipLaunchKernelGGL(sparse_project_kernel<double>, grid, dim3(kThreads), 0, s, (int)r, (int)I, (int)q, nb, C,
-                       (const int32_t*)colptr, (const int32_t*)blk_i, (const double*)V, ldv, (const double*)U, su_row, su_col,
-                       (double*)W, ldw);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(sparse_project_kernel<T>, grid, dim3(kThreads), 0, s, (int)r, (int)I, (int)q, nb, C, (const int32_t*)colptr,
+                       (const int32_t*)blk_i, (const T*)V, ldv, (const T*)U, su_row, su_col, (T*)W, ldw);
+  });
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }

@@ -17,7 +17,7 @@
 // MFMA rate, which equals the vector rate on gfx950), 32 for the projection to rank 32 (AI = 11 flop/B: HBM-bound).
 #include <type_traits>
 
-#include "ttr_common.h"
+#include "detail/ttr_internal.h"
 
 namespace ttr {
 
@@ -57,10 +57,6 @@ __host__ __device__ inline void split_range(int64_t chunks, int nsplit, int spli
 }
 
 // N consecutive elements with one (or two) wide loads when the caller established the alignment, element-wise otherwise
-template <typename T, int N>
-struct Pack {
-  T v[N];
-};
 template <typename T, int N>
 __device__ __forceinline__ Pack<T, N> load_pack(const T* __restrict__ p, bool aligned, int64_t valid) {
   Pack<T, N> out;

@@ -150,17 +150,6 @@ __global__ void spectrum_flat_kernel(int64_t batch, int n, int keep, T thr, cons
   flat[b] = (ok && sg(kp - 1) >= thr * s0) ? 1 : 0;
 }
 
-// Block-wide sum of doubles (256 threads), result in every thread.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();  // `red` may still be read from a previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0;
-  for (int w = 0; w < kThreads / kWave; ++w) s += red[w];
-  return s;
-}
-
 // flag[b] = 1 when rows 32.. of the 64-row matrix R[b] hold at most (c eps)^2 of its squared Frobenius norm -- the packing test of
 // the fused push + factor kernel (ttr_qr.hip: `packed`), for the LAST core of a sweep, which no push follows
 template <typename T>
@@ -225,13 +214,6 @@ __global__ __launch_bounds__(kThreads) void scale_batch_kernel(const T* __restri
 
 using namespace ttr;
 
-// f(float{}) or f(double{}): every entry below launches the float or the double instance of ONE kernel with the same arguments
-template <typename F>
-static void by_dtype(int dtype, F&& f) {
-  if (dtype == TTR_F32) f(float{});
-  else f(double{});
-}
-
 extern "C" {
 
 int ttr_norm(int dtype, int64_t count, int64_t batch, const void* x, int64_t stride_x, void* out, void* stream) {
@@ -257,7 +239,7 @@ int ttr_scale_cols(int dtype, int64_t rows, int64_t cols, int64_t batch, const v
   if (rows <= 0 || cols <= 0 || batch <= 0) return TTR_OK;
   TTR_REQUIRE(in && sc && out, TTR_E_INVALID, "ttr_scale_cols: null pointer");
   if (batch > 65535) {  // the batch is a grid dimension: slices
-    const int64_t elem = dtype == TTR_F64 ? 8 : 4;
+    const int64_t elem = elem_size(dtype);
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
       const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
       const int rc = ttr_scale_cols(dtype, rows, cols, nb, (const char*)in + b0 * stride_in * elem, ldi, stride_in,
@@ -369,7 +351,7 @@ int ttr_scale_batch(int dtype, int64_t count, int64_t batch, const void* x, int6
   ProfScope prof(TTR_PROF_MISC, s);
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {  // gridDim.y limit
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
-    const int64_t so = dtype == TTR_F32 ? 4 : 8;
+    const int64_t so = elem_size(dtype);
     const char* xs = (const char*)x + b0 * stride_x * so;
     char* os = (char*)out + b0 * stride_out * so;
     const char* ss = scale ? (const char*)scale + b0 * stride_scale * so : nullptr;
