@@ -1027,6 +1027,39 @@ int64_t ttr_mode_sandwich_workspace_bytes(int dtype, int64_t S, int64_t R, int64
 int ttr_mode_sandwich(int dtype, int64_t S, int64_t R, int64_t I, int64_t C, const void* Z, const void* A, const int64_t* a_strides,
                       const void* w, const void* mu, void* Q, void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * The minimisation step of TT-cross (added under ABI 17; cross.py:342-359, the `_minimize` branch of `evaluate_function` behind
+ * `minimum` / `argmin` / `maximum` / `argmax`): one call per evaluated fibre block, in place, one pass over it.
+ *
+ * ttr_minimize_step   e[m] <- pi/2 - atan(e[m] - m0) for every m < M = Ra I Rb, and the running best sample updated from e
+ *
+ * `e` [M] contiguous device elements of the dtype, aligned to the element size (NOT necessarily to 16 bytes: a sliced view is
+ * taken where it lies), read as the block [Ra, I, Rb].  The state, on the device: `best` one element of the dtype, `pos` int64 [N]
+ * with N = nl + 1 + nr, `flags` int32 [2] = (found, invalid); the caller zeroes `flags` before the first call.  `lset` int64
+ * [Ra, nl + 1] with the row stride ld_lset (elements), column 0 unused (cross.py's dummy column); `rset` int64 [Rb, nr + 1] with
+ * the row stride ld_rset, last column unused.
+ *   m0 = found ? best : 0, read before anything is written; the transform is computed in the dtype (atanf / atan).
+ *   m* = the FIRST index at which the original e is smallest among its finite entries (-0.0 and +0.0 compare equal).
+ *   A non-finite entry never wins and sets invalid = 1; then `best`, `pos` and `found` are left alone (what such an entry is
+ *   transformed to is unspecified; every finite entry is still transformed).  invalid is never cleared.
+ *   Otherwise, where !found or e[m*] < best (strictly): best = e[m*] (the sample itself), found = 1, and with
+ *   m* = (a I + i) Rb + c: pos = lset[a, 1:] ++ [i] ++ rset[c, :-1].  Else `best`, `pos` and `found` are not written.
+ * Two launches on `stream`: a streaming pass (16-byte loads and stores on the aligned part of e; a workgroup owns whole chunks of
+ * TTR_MINIMIZE_BLOCK_ELEMS consecutive elements, chunk c going to workgroup c mod 2048; per lane the lexicographic minimum of
+ * (value, index), combined across the wave and through LDS; one partial per workgroup into `workspace`), then one workgroup that
+ * reduces the partials and updates the state.  All comparisons are exact and (value, index) is a total order: the result does not
+ * depend on the reduction order, the same call gives the same bits.  No atomics, no host synchronisation, 64-bit indices.
+ * ttr_minimize_workspace_bytes(dtype, M): the bytes of `workspace` (8-byte aligned); TTR_E_INVALID (< 0) for a bad dtype or M < 1.
+ * Before any launch, with e and the state untouched: TTR_E_INVALID for a bad dtype, an extent < 1, nl or nr < 0, a row stride
+ * below its row length, a null or misaligned pointer; TTR_E_UNSUPPORTED for a block or index set beyond 2^57 elements;
+ * TTR_E_WORKSPACE for a missing or short workspace.  Profiling kind: TTR_PROF_MISC.
+ */
+#define TTR_MINIMIZE_BLOCK_ELEMS 4096
+int64_t ttr_minimize_workspace_bytes(int dtype, int64_t M);
+int ttr_minimize_step(int dtype, void* e, int64_t Ra, int64_t I, int64_t Rb, const void* lset, int64_t ld_lset, int64_t nl,
+                      const void* rset, int64_t ld_rset, int64_t nr, void* best, void* pos, void* flags, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

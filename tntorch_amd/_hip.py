@@ -992,6 +992,46 @@ def maxvol(A: torch.Tensor, tol: float, max_iters: int, status: Optional[torch.T
     return index, C
 
 
+def minimize_workspace_bytes(dt: torch.dtype, M: int) -> int:
+    """ttr_minimize_workspace_bytes; a negative status (a bad dtype, M < 1) is returned."""
+    return int(lib().ttr_minimize_workspace_bytes(dtype_code(dt), int(M)))
+
+
+@_on_device
+def minimize_step(e: torch.Tensor, Ra: int, I: int, Rb: int, lset: torch.Tensor, rset: torch.Tensor, best: torch.Tensor,
+                  pos: torch.Tensor, flags: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_minimize_step, in place: e [Ra * I * Rb] (unit stride; a view that starts off a 16-byte boundary is taken where it
+    lies) <- pi/2 - atan(e - m0), m0 = the best value so far (0 before the first), and the state ``best`` (one element of e's
+    dtype), ``pos`` (int64 [nl + 1 + nr]), ``flags`` (int32 [2]: found, invalid; zeroed by the caller before the first call)
+    updated from the first smallest finite entry of the original e, where that is strictly smaller than ``best`` (or nothing was
+    found yet): pos = lset[a, 1:] ++ [i] ++ rset[c, :-1].  ``lset`` int64 [Ra, nl + 1], ``rset`` int64 [Rb, nr + 1], unit column
+    stride, any row stride.  ``workspace``: a uint8 device tensor of at least minimize_workspace_bytes(...) bytes (allocated here
+    when None).  Nothing is read back.  Returns e."""
+    dt = dtype_code(e.dtype)
+    Ra, I, Rb = int(Ra), int(I), int(Rb)
+    M = Ra * I * Rb
+    if not (e.dim() == 1 and e.shape[0] == M and (M == 1 or e.stride(0) == 1)):
+        raise ValueError("minimize_step: e must be a unit-stride vector of Ra * I * Rb = {} elements".format(M))
+    for name, s, rows in (("lset", lset, Ra), ("rset", rset, Rb)):
+        if not (s.dim() == 2 and s.dtype == torch.int64 and s.device == e.device and s.shape[0] == rows and s.shape[1] >= 1
+                and (s.shape[1] == 1 or s.stride(1) == 1) and (rows == 1 or s.stride(0) >= s.shape[1])):
+            raise ValueError("minimize_step: {} must be an int64 [{}, n + 1] matrix on e's device with unit column stride".format(name, rows))
+    nl, nr = lset.shape[1] - 1, rset.shape[1] - 1
+    if not (best.dtype == e.dtype and best.numel() == 1 and best.device == e.device):
+        raise ValueError("minimize_step: best must be one element of e's dtype on e's device")
+    if not (pos.dtype == torch.int64 and pos.dim() == 1 and pos.shape[0] == nl + 1 + nr and pos.is_contiguous() and pos.device == e.device):
+        raise ValueError("minimize_step: pos must be a contiguous int64 vector of nl + 1 + nr = {} elements on e's device".format(nl + 1 + nr))
+    if not (flags.dtype == torch.int32 and flags.dim() == 1 and flags.shape[0] == 2 and flags.is_contiguous() and flags.device == e.device):
+        raise ValueError("minimize_step: flags must be a contiguous int32 [2] vector on e's device")
+    wsb = minimize_workspace_bytes(e.dtype, M)
+    if wsb < 0:
+        _check(wsb, "ttr_minimize_workspace_bytes")
+    ws = workspace if workspace is not None else _workspace(wsb, e.device)
+    _call("ttr_minimize_step", dt, e.data_ptr(), Ra, I, Rb, lset.data_ptr(), int(lset.stride(0)) if Ra > 1 else nl + 1, nl,
+          rset.data_ptr(), int(rset.stride(0)) if Rb > 1 else nr + 1, nr, best.data_ptr(), pos.data_ptr(), flags.data_ptr(),
+          ws.data_ptr(), int(ws.numel()))
+    return e
+
 
 def als_normal_groups(r0: int, r1: int) -> int:
     return int(lib().ttr_als_normal_groups(int(r0), int(r1)))

@@ -2035,6 +2035,16 @@ def gather_step(X: torch.Tensor, xrow, G: torch.Tensor, idx: torch.Tensor) -> to
     return _hip.gather_step(X, xrow, G, idx)
 
 
+MIN_BLOCK_ELEMS = _hip.MINIMIZE_BLOCK_ELEMS  # elements of one workgroup's chunk in ttr_minimize_step (the header's constant)
+
+
+def minimize_step(e: torch.Tensor, Ra: int, I: int, Rb: int, lset: torch.Tensor, rset: torch.Tensor, best: torch.Tensor,
+                  pos: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """cross.py:342-359 (ttr_minimize_step), in place and without a readback: e <- pi/2 - atan(e - m0) and the running best
+    sample (``best``, ``pos``, ``flags`` = (found, invalid)) updated from the first smallest finite entry of the original e."""
+    return _hip.minimize_step(e, Ra, I, Rb, lset, rset, best, pos, flags)
+
+
 # ------------------------------------------------------------------------------------------------ TT completion (ALS)
 ALS_WORKSPACE_BYTES = 1 << 30  # device bytes of one core step's systems; a step above it runs in chunks of slices
 ALS_TASK_SAMPLES = 1024  # samples per ttr_als_normal task (at least; 16 K for K > 64): long slices are split into several

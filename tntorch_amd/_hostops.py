@@ -686,6 +686,32 @@ def maxvol(A3: torch.Tensor, tol: float, max_iters: int):
     return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
 
 
+def minimize_step(e: torch.Tensor, Ra: int, I: int, Rb: int, lset: torch.Tensor, rset: torch.Tensor, best: torch.Tensor,
+                  pos: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """Mirror of ttr_minimize_step, in place: e [Ra * I * Rb] <- pi/2 - atan(e - m0) in e's dtype, m0 = best if flags[0] (found)
+    else 0; the state ``best`` (one element), ``pos`` (int64 [nl + 1 + nr]), ``flags`` (int32 [2]: found, invalid) is updated from
+    the FIRST smallest entry of the original e (-0.0 == +0.0) where that is strictly smaller than ``best`` or nothing was found
+    yet: pos = lset[a, 1:] ++ [i] ++ rset[c, :-1] for the entry (a I + i) Rb + c.  A non-finite entry sets flags[1] and leaves
+    the rest of the state alone."""
+    assert e.dim() == 1 and e.shape[0] == Ra * I * Rb and lset.shape[0] == Ra and rset.shape[0] == Rb
+    found = bool(flags[0])
+    orig = e.clone()
+    m0 = best.reshape(()).clone() if found else torch.zeros((), dtype=e.dtype)
+    e.copy_(math.pi / 2 - torch.atan(orig - m0))
+    if not bool(torch.isfinite(orig).all()):
+        flags[1] = 1
+        return e
+    v = orig.min()
+    if found and not bool(v < best.reshape(())):
+        return e
+    m = int(torch.nonzero(orig == v)[0])
+    a, i, c = m // (I * Rb), (m // Rb) % I, m % Rb
+    best.reshape(-1)[0] = orig[m]
+    flags[0] = 1
+    pos.copy_(torch.cat([lset[a, 1:], torch.tensor([i], dtype=torch.int64), rset[c, : rset.shape[1] - 1]]))
+    return e
+
+
 def als_core(L: torch.Tensor, R: torch.Tensor, w: torch.Tensor, y: torch.Tensor, order: torch.Tensor, off: Sequence[int],
              I: int) -> torch.Tensor:
     """interpolation.py:71-90 with the design columns in (a, b) order: slice i of the new core [r0, I, r1] is the minimum-norm

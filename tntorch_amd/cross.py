@@ -12,8 +12,19 @@ and the interface update as one ``ttr_gather_step`` launch per input tensor.  In
 value back to the host (validation error and invalid-value flag together).  Right interfaces are kept transposed (``[P, r]``)
 on the device, so that every update is a row-gathered product.
 
-``_minimize`` and the functions built on it (``minimum``, ``maximum``, ``argmin``, ``argmax``), ``cross_forward`` and
-``rect_maxvol`` are out of scope.
+``minimum``, ``argmin``, ``maximum`` and ``argmax`` (cross.py:12-109) run ``cross(..., _minimize=True)``: every evaluated fibre
+block goes through Oseledets' map ``pi/2 - atan(f - best)``, so that maxvol steers the index sets towards small values, and the
+best sample seen is carried along.  That is one ``minimize_step`` per block (``ttr_minimize_step`` on the device: one pass over
+the block, the running best kept in device memory, nothing read back; its mirror on the CPU), and both maxvol calls become
+``maxvol(Q, 1.05, 10)``, which is what the reference's ``rect_maxvol(Q, maxK=Q.shape[1])`` computes (it adds no rows).
+
+Unlike the reference: the best value is the evaluated sample itself, not ``tan(pi/2 - y) + min`` (a round trip that loses
+digits as ``|f - min|`` grows); the winning sample of a block is the first smallest ``f``, not the first largest transformed
+value (the map can round distinct values together); a ``found`` flag replaces the ``info["min"] == 0`` sentinel, so a function
+whose minimum is exactly 0 keeps it; a non-finite sample raises ``ValueError`` (the map sends ``+Inf`` to a finite value).  Batched
+tensors, CP cores on the device and ranks above 128 on the device are refused as for ``cross``.
+
+``cross_forward`` and a public ``rect_maxvol`` are out of scope.
 """
 
 from __future__ import annotations
@@ -26,7 +37,7 @@ from typing import Any, Callable, Sequence, Union
 import numpy as np
 import torch
 
-__all__ = ["cross"]
+__all__ = ["cross", "minimum", "argmin", "maximum", "argmax"]
 
 MAX_DEVICE_RANK = 128  # ttr_maxvol's limit (r x r inverse in LDS): device cores take no larger bond
 
@@ -113,6 +124,7 @@ def cross(
     verbose: bool = True,
     return_info: bool = False,
     record_samples: bool = False,
+    _minimize: bool = False,
     device: Any = None,
     suppress_warnings: bool = False,
     detach_evaluations: bool = False,
@@ -135,6 +147,7 @@ def cross(
 
     :return: an N-dimensional TT :class:`Tensor` (and a dictionary, if ``return_info``)
     """
+    from . import _hostops
     from .maxvol import maxvol
     from .tensor import Tensor
     from .tools import meshgrid
@@ -244,6 +257,11 @@ def cross(
         info["sample_positions"] = torch.zeros(0, N).to(device)
         info["sample_values"] = torch.zeros(0).to(device)
     invalid_dev = [torch.zeros((), dtype=torch.bool, device=device)] if on_dev else None
+    if _minimize:  # the running best sample, on the tensors' device: value, position, (found, invalid)
+        minimize_step = _hipops.minimize_step if on_dev else _hostops.minimize_step
+        min_best = torch.zeros(1, dtype=dtype, device=device)
+        min_pos = torch.zeros(N, dtype=torch.int64, device=device)
+        min_flags = torch.zeros(2, dtype=torch.int32, device=device)
 
     def evaluate_function(j):  # the function over Rs[j] x Is[j] x Rs[j+1] fibres (cross.py:321-394)
         Xs = []
@@ -262,7 +280,10 @@ def cross(
         info["eval_time"] += time.time() - eval_start
         if evaluation.dim() == 2:
             evaluation = evaluation[:, 0]
-        if on_dev:  # checked at the end of the sweep, with the validation error (no readback here)
+        if on_dev and _minimize:  # ttr_minimize_step sets the invalid flag in the pass that transforms the block
+            evaluation = evaluation.to(dtype).contiguous()
+            minimize_step(evaluation, Rs[j], Is[j], Rs[j + 1], lsets[j], rsets[j], min_best, min_pos, min_flags)
+        elif on_dev:  # checked at the end of the sweep, with the validation error (no readback here)
             invalid_dev[0] = invalid_dev[0] | ~torch.isfinite(evaluation).all()
         else:
             invalid = torch.nonzero(torch.isnan(evaluation) | torch.isinf(evaluation))
@@ -275,6 +296,10 @@ def cross(
                         f(*[x[invalid : invalid + 1][:, None] for x in Xs]).item(),
                     )
                 )
+            if _minimize:  # (on a copy: the function may have returned its argument, or a tensor autograd tracks)
+                evaluation = evaluation.detach().to(dtype).clone()
+                minimize_step(evaluation, Rs[j], Is[j], Rs[j + 1], torch.as_tensor(lsets[j], dtype=torch.int64),
+                              torch.as_tensor(rsets[j], dtype=torch.int64), min_best, min_pos, min_flags)
         V = torch.reshape(evaluation, [Rs[j], Is[j], Rs[j + 1]])
         info["nsamples"] += V.numel()
         return V
@@ -291,7 +316,7 @@ def cross(
             V = torch.reshape(evaluate_function(j), [-1, Rs[j + 1]])
             if on_dev:
                 Q = _hipops.qr(V.detach()[None])[0][0]
-                local, C = maxvol(Q)
+                local, C = maxvol(Q, 1.05, 10) if _minimize else maxvol(Q)
                 cores[j] = C.reshape(Rs[j], Is[j], Rs[j + 1])
                 local_r, local_i = local // Is[j], local % Is[j]
                 lsets[j + 1] = torch.cat([lsets[j][local_r, :], local_i[:, None]], dim=1)
@@ -299,7 +324,7 @@ def cross(
                     t_linterfaces[k][j + 1] = _hipops.gather_step(t_linterfaces[k][j], local_r, t.cores[j], local_i)
             else:
                 Q, _ = torch.linalg.qr(V)
-                local, _ = maxvol(Q.detach())
+                local, _ = maxvol(Q.detach(), 1.05, 10) if _minimize else maxvol(Q.detach())
                 local = local.numpy()
                 cores[j] = torch.reshape(torch.linalg.lstsq(Q[local, :].t(), Q.t()).solution.t(), [Rs[j], Is[j], Rs[j + 1]])
                 local_r, local_i = np.unravel_index(local, [Rs[j], Is[j]])
@@ -318,7 +343,7 @@ def cross(
             V = torch.reshape(evaluate_function(j), [Rs[j], -1])
             if on_dev:
                 Q = _hipops.qr(V.detach().t()[None])[0][0]
-                local, C = maxvol(Q)
+                local, C = maxvol(Q, 1.05, 10) if _minimize else maxvol(Q)
                 cores[j] = C.t().contiguous().reshape(Rs[j], Is[j], Rs[j + 1])
                 local_i, local_r = local // Rs[j + 1], local % Rs[j + 1]
                 rsets[j - 1] = torch.cat([local_i[:, None], rsets[j][local_r, :]], dim=1)
@@ -326,7 +351,7 @@ def cross(
                     t_rinterfaces[k][j - 1] = _hipops.gather_step(t_rinterfaces[k][j], local_r, t.cores[j].permute(2, 1, 0), local_i)
             else:
                 Q, _ = torch.linalg.qr(V.t())
-                local, _ = maxvol(Q.detach())
+                local, _ = maxvol(Q.detach(), 1.05, 10) if _minimize else maxvol(Q.detach())
                 local = local.numpy()
                 cores[j] = torch.reshape(torch.linalg.lstsq(Q[local, :].t(), Q.t()).solution, [Rs[j], Is[j], Rs[j + 1]])
                 local_i, local_r = np.unravel_index(local, [Is[j], Rs[j + 1]])
@@ -345,18 +370,26 @@ def cross(
         # Validation error: the one readback of the sweep
         if on_dev:
             val_eps = _hip.norm((ys_val - _chain_dev(cores, Xs_val)).reshape(1, -1))[0] / norm_ys_val
-            host = torch.stack([val_eps.double(), invalid_dev[0].double()]).cpu()
+            if _minimize:
+                host = torch.stack([val_eps.double(), min_flags[1].double(), min_best[0].double()]).cpu()
+            else:
+                host = torch.stack([val_eps.double(), invalid_dev[0].double()]).cpu()
             if host[1].item():
                 raise ValueError("Invalid return value for function {}: NaN or Inf among the samples of sweep {}".format(function, i))
             val_eps_host = host[0].item()
+            best_host = host[2].item() if _minimize else None
         else:
             val_eps = torch.norm(ys_val - Tensor(cores)[Xs_val].torch()) / norm_ys_val
             val_eps_host = val_eps
+            best_host = min_best[0].item() if _minimize else None
         info["val_epss"].append(val_eps)
         if val_eps_host < eps:
             converged = True
         if verbose:
-            print("| eps: {:.3e}".format(float(val_eps_host)), end="")
+            if _minimize:
+                print("| best: {:.8g}".format(best_host), end="")
+            else:
+                print("| eps: {:.3e}".format(float(val_eps_host)), end="")
             print(" | time: {:8.4f} | largest rank: {:3d}".format(time.time() - start, max(Rs)), end="")
             if converged:
                 print(" <- converged: eps < {}".format(eps))
@@ -387,7 +420,11 @@ def cross(
             Rs = newRs
             t_linterfaces, t_rinterfaces = init_interfaces(tensors, rsets, N, device, dtype)
 
-    if val_eps_host > eps and not suppress_warnings:
+    if _minimize:  # read once, after the last sweep: the position (the value stays where the tensors are)
+        info["min"] = min_best[0].clone()
+        info["argmin"] = tuple(int(x) for x in min_pos.tolist())
+
+    if val_eps_host > eps and not _minimize and not suppress_warnings:
         logging.warning("eps={:g} (larger than {}) when cross-approximating {}".format(float(val_eps_host), eps, function))
 
     if verbose:
@@ -411,3 +448,44 @@ def cross(
         info["val_eps"] = val_eps
         return ret, info
     return ret
+
+
+def _optimum(tensors, function, rmax, max_iter, verbose, kwargs):
+    _, info = cross(**kwargs, tensors=tensors, function=function, rmax=rmax, max_iter=max_iter, verbose=verbose, return_info=True,
+                    _minimize=True)
+    return info
+
+
+def minimum(tensors=None, function=lambda x: x, rmax=10, max_iter=10, verbose=False, **kwargs):
+    """Estimate the minimal element of a tensor, or of a function of one or several tensors (cross.py:12-37), by
+    cross-approximation of ``pi/2 - atan(f - best)``.
+
+    :param tensors: a :class:`Tensor` or a list of them (or pass ``domain=`` among the keyword arguments)
+    :param function: applied to the tensors' entries (default: identity)
+    :param rmax: passed to :func:`cross`; lower is faster, higher is more thorough (default 10)
+    :param max_iter: passed to :func:`cross` (default 10)
+    :param verbose: default False
+    :param kwargs: passed to :func:`cross`
+
+    :return: a 0-dim tensor on the tensors' device, in their dtype: the smallest sample that was evaluated (the sample itself,
+        unlike the reference's ``tan`` round trip)
+    """
+    return _optimum(tensors, function, rmax, max_iter, verbose, kwargs)["min"]
+
+
+def argmin(tensors=None, function=lambda x: x, rmax=10, max_iter=10, verbose=False, **kwargs):
+    """Estimate the position of the minimal element (cross.py:40-61); arguments as for :func:`minimum`.
+
+    :return: a tuple of N Python ints
+    """
+    return _optimum(tensors, function, rmax, max_iter, verbose, kwargs)["argmin"]
+
+
+def maximum(tensors=None, function=lambda x: x, rmax=10, max_iter=10, verbose=False, **kwargs):
+    """Estimate the maximal element (cross.py:64-85): :func:`minimum` of the negated function, negated."""
+    return -_optimum(tensors, lambda *x: -function(*x), rmax, max_iter, verbose, kwargs)["min"]
+
+
+def argmax(tensors=None, function=lambda x: x, rmax=10, max_iter=10, verbose=False, **kwargs):
+    """Estimate the position of the maximal element (cross.py:88-109): :func:`argmin` of the negated function."""
+    return _optimum(tensors, lambda *x: -function(*x), rmax, max_iter, verbose, kwargs)["argmin"]
