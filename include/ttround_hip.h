@@ -665,9 +665,10 @@ int ttr_debug_set_qr_stamps(void* device_buffer);
 /*   TTR_KNOB_EIGH_SMALL  1 = ttr_eigh_top and the tridiagonal solver of ttr_eigh_trunc (TTR_EIG_RAW / REF) on 64 x 64
  *                      matrices first run the 32-row instance of their kernel over the zero-tail items (Gram matrices of packed
  *                      bonds) and then the 64-row one over the rest; 0 = one launch, the 64-row instance shrinks such items
- *                      itself (A/B); 2 (default) = 1, and fp32 ttr_eigh_top launches of >= 1024 matrices use a build of the 32-row
- *                      instance capped at 168 VGPRs (three waves per SIMD, 44 spilled registers; 3: 128 VGPRs, four waves) --
- *                      same results bit for bit, 17 % less eigensolver time at B = 4096. */
+ *                      itself (A/B); 2 (default) = 1, and fp32 ttr_eigh_top launches of >= 1024 matrices use the lean build of the
+ *                      32-row instance: pivots of the twisted factorisation in LDS, 108 VGPRs under the 128-register cap of four
+ *                      waves per SIMD, no scratch (1: 208 VGPRs, two waves) -- same results bit for bit; 3 = the 128-register
+ *                      cap, which is that same build. */
 #define TTR_KNOB_EIGH_SMALL 8
 int ttr_debug_set_knob(int knob, int value);
 int ttr_prof_enable(int on);   /* 0 = off, 1 = per-kind device times, 2 = times + executed-work census (ttr_prof_collect_work) */

@@ -73,6 +73,9 @@ struct EighArgs {
   int top_need_all;          // != 0: the top-r path only serves items of which it computes EVERY eigenpair (top_r >= the live size)
   const int32_t* skip_flag;  // != 0 on the device: the driver has converged, the launch returns at once
   int32_t* rot_count;        // incremented once per problem that rotated anything (the driver's "a whole sweep found nothing")
+#ifdef TTR_EIGH_STAMPS
+  long long stamp_block;     // diagnostics build: the block whose phases are stamped (0, or one in the middle of a loaded launch)
+#endif
 };
 
 constexpr int kMaxPairs = 2048;  // n <= 4096 (fp32) / 2048 (fp64) in the global-memory variant: its rotation table and
@@ -586,6 +589,9 @@ template <typename T, bool TOP = false, int NMAX = 64, int MINW = 0>
 __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NMAX == 64 ? 4 : 2))) void eigh_tridiag_kernel(EighArgs<T> p) {
   static_assert(NMAX == 64 || NMAX == 32, "64-row kernel and its 32-row instance");
   constexpr int NT = NMAX / 16;   // 16-row tiles
+  // The lean large-launch build (fp32 top-r, 32 rows, four waves per SIMD = 128 registers, no scratch): the pivots of the
+  // twisted factorisation live in LDS and its recurrences are loops, see `select` below
+  constexpr bool LEAN = TOP && NMAX == 32 && MINW == 4 && sizeof(T) == 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -644,8 +650,15 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
   constexpr int kSel16 = 16 / (int)sizeof(T);
   T* const dsel = A + ((n * ld + 3 + 408 + 66 * 2 + 64 + 16 * 17 + 8 + kSel16 - 1) / kSel16) * kSel16;   // [64]
   T* const e2s = dsel + 64;                                                                                 // [64]
+  // LEAN: D+_i / D-_i of this lane's vector at dpl / dml[32 i]; a wave has at most 16 vectors (lanes 0 .. 15), the other lanes
+  // compute along on a copy of theirs and store nothing
+  T* const dpl = e2s + 64 + 16 * wv + (lane & 15);   // [32][2][16]
+  T* const dml = dpl + 32 * 32;                      // [32][2][16]
 
   const T* __restrict__ G = p.G + bt * p.strideG;
+#ifdef TTR_EIGH_STAMPS
+  if (p.ws && bt == p.stamp_block && tid == 0) reinterpret_cast<long long*>(p.ws)[31] = (long long)clock64();   // block entry: slot 31
+#endif
   // ---- load + scale (both waves)
   if ((n == 64 || (n == 32 && nf == 64)) && p.ldg == 64 && (p.stride_gpart & 3) == 0 &&
       (reinterpret_cast<uintptr_t>(G) & (4 * sizeof(T) - 1)) == 0) {
@@ -699,11 +712,11 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
   __syncthreads();
 
 #ifdef TTR_EIGH_STAMPS
-  long long* const dbg = reinterpret_cast<long long*>(p.ws);  // diagnostics build: cycle stamps of matrix 0 (wave 0)
+  long long* const dbg = reinterpret_cast<long long*>(p.ws);  // diagnostics build: cycle stamps of block p.stamp_block (wave 0)
   int dbgi = 0;
-#define TTR_ESTAMP() do { if (dbg && bt == 0 && tid == 0) dbg[dbgi++] = (long long)clock64(); } while (0)
+#define TTR_ESTAMP() do { if (dbg && bt == p.stamp_block && tid == 0) dbg[dbgi++] = (long long)clock64(); } while (0)
   int dbgj = 32;  // wave 1's stamps (lane 0 of wave 1) go to slots 32..
-#define TTR_ESTAMP1() do { if (dbg && bt == 0 && tid == kWave) dbg[dbgj++] = (long long)clock64(); } while (0)
+#define TTR_ESTAMP1() do { if (dbg && bt == p.stamp_block && tid == kWave) dbg[dbgj++] = (long long)clock64(); } while (0)
 #else
 #define TTR_ESTAMP() do {} while (0)
 #define TTR_ESTAMP1() do {} while (0)
@@ -816,8 +829,42 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
     const T lam_grp = T(0.5) * (lo + hi);
     if (live && gs == 0) lamv[gj] = lam_grp;
     lam_vec = __shfl(lam_grp, (lane < nvec ? lane : 0) * (kp >= 2 ? GL : 0), 64);
+    TTR_ESTAMP();   // (multisection done; whichever wave this is)
+    TTR_ESTAMP1();
     // twisted factorisation: D+ from the top, gamma from the bottom, then D- kept above the twist
     const T lam = lam_vec;
+    if constexpr (LEAN) {
+      // The unrolled form below is one straight-line block at n = 32, in which the compiler shares every e_i^2, d_i - lambda
+      // and 1 / D+_i between the three recurrences and the vector pass: 32 registers each on top of the 32 pivots and wave 1's 16
+      // accumulators (208 in all; 125 of them spilled to scratch under the cap of 128).  Here the recurrences are loops over
+      // pivots in LDS, d / e come from LDS (broadcast reads off the chain) and the D- recurrence runs ONCE: the gamma pass and
+      // the D- pass feed the same clamped pivot into the same division, so the one chain yields gamma_i from the raw pivot and
+      // stores the clamped one for every i; the vector pass reads D- only above the twist.  Same operations on the same values
+      // in the same order, with the contractions of the unrolled form spelled out.
+      const bool own = lane < 16;
+      T q = dv[0] - lam;
+#pragma unroll 4
+      for (int i = 0; i < 32; ++i) {
+        if (fabs(q) < pivmin) q = -pivmin;
+        if (own) dpl[32 * i] = q;
+        if (i + 1 < 32) { const T e = ev[i]; q = __builtin_fmaf(-(e * e), __builtin_amdgcn_rcpf(q), dv[i + 1] - lam); }
+      }
+      T qm = dv[31] - lam;
+      T best = fabs((dpl[32 * 31] + qm) - qm);
+      twist = 31;
+      if (fabs(qm) < pivmin) qm = -pivmin;
+      if (own) dml[32 * 31] = qm;
+#pragma unroll 4
+      for (int i = 30; i >= 0; --i) {
+        const T e = ev[i], dl = dv[i] - lam;
+        qm = __builtin_fmaf(-(e * e), __builtin_amdgcn_rcpf(qm), dl);
+        const T gam = (dpl[32 * i] + qm) - dl;
+        if (fabs(gam) < best) { best = fabs(gam); twist = i; }
+        if (fabs(qm) < pivmin) qm = -pivmin;
+        if (own) dml[32 * i] = qm;
+      }
+      return;
+    }
     T q = dv[0] - lam;
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) {
@@ -859,6 +906,22 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
   // x_twist = 1;  x_i = -(e_i / D+_i) x_{i+1} (i < twist);  x_{i+1} = -(e_i / D-_{i+1}) x_i (i >= twist).  WRITE = false: only ||x||^2.
   auto vector_pass = [&](auto WRITE, T scale) __attribute__((always_inline)) -> T {
     constexpr bool kWrite = decltype(WRITE)::value != 0;
+    if constexpr (LEAN) {   // (live lanes only: their own pivots)
+      T nrm2 = T(1), xc = T(1);
+      if (kWrite) A[twist * ZLD + jv] = scale;
+      for (int i = twist - 1; i >= 0; --i) {  // upwards
+        xc = -(ev[i] * __builtin_amdgcn_rcpf(dpl[32 * i])) * xc;
+        nrm2 = __builtin_fmaf(xc, xc, nrm2);
+        if (kWrite) A[i * ZLD + jv] = xc * scale;
+      }
+      xc = T(1);
+      for (int i = twist; i < 31; ++i) {  // downwards
+        xc = -(ev[i] * __builtin_amdgcn_rcpf(dml[32 * (i + 1)])) * xc;
+        nrm2 = __builtin_fmaf(xc, xc, nrm2);
+        if (kWrite) A[(i + 1) * ZLD + jv] = xc * scale;
+      }
+      return nrm2;
+    }
     T nrm2 = T(1), xc = T(0);
     if (kWrite && twist < n) A[twist * ZLD + jv] = scale;
 #pragma unroll
@@ -1098,6 +1161,7 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
         }
         TTR_ESTAMP();
         __syncthreads();  // B2: Z complete
+        TTR_ESTAMP();
         taken = badf[0] == 0;
       }
       if (taken) {
@@ -1113,13 +1177,15 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
           if (p.top_flat) p.top_flat[bt] = 1;
           if (p.sweeps) p.sweeps[bt] = 0;
         }
-        T* __restrict__ Vo = p.V + bt * p.strideV;
-        const int zc = n - rsel;
-        for (int idx = lane; idx < n * zc; idx += kWave) {
-          const int row = idx / zc, c = rsel + idx - row * zc;
-          Vo[(int64_t)row * p.ldv + c] = T(0);
+        if constexpr (!LEAN) {   // (LEAN: wave 1 wrote these zeros while it waited for the first reflector block)
+          T* __restrict__ Vo = p.V + bt * p.strideV;
+          const int zc = n - rsel;
+          for (int idx = lane; idx < n * zc; idx += kWave) {
+            const int row = idx / zc, c = rsel + idx - row * zc;
+            Vo[(int64_t)row * p.ldv + c] = T(0);
+          }
+          pad_tail(false, lane, kWave);
         }
-        pad_tail(false, lane, kWave);
         TTR_ESTAMP();
         return;
       }
@@ -1218,6 +1284,18 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
     if (lane < n) dv[lane] = dreg;  // eigenvalues for the epilogue (wave 1 is past its last replay: buffer 1 is free)
   } else {
     // ---- 2. X = Q^T = H_{n-2} ... H_0 on the matrix cores, forward over the reflector blocks:  X <- (I - V_b T_b^T V_b^T) X
+    if constexpr (LEAN) {
+      // Everything a taken item leaves as zeros -- V beyond its r kept columns and its 32 x 32 block, sigma[32 ..] -- is written
+      // HERE, while this wave waits for wave 0's first 16 reflectors anyway: at the end of the block these 3072+ four-byte stores
+      // were wave 0's alone and the last thing the block did (19 - 25 k of its ~110 k cycles under load, wave 1 long finished).  A
+      // declined item overwrites all of it in the QL epilogue, many barriers later.  (This instance: nf = 64, n = 32.)
+      T* __restrict__ Vp = p.V + bt * p.strideV;
+      for (int idx = lane; idx < 64 * 64; idx += kWave) {
+        const int row = idx >> 6, j = idx & 63;
+        if (row >= 32 || j >= rsel) Vp[(int64_t)row * p.ldv + j] = T(0);
+      }
+      if (lane < 32) p.sigma[bt * p.stride_sigma + 32 + lane] = T(0);
+    }
     {
       using MF = Mfma<T>;
       using Acc = typename MF::Acc;
@@ -1321,6 +1399,7 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
         select();
         TTR_ESTAMP1();
         __syncthreads();  // B1
+        TTR_ESTAMP1();
         bool taken = qualifies();
         if (taken) {
           if (vlive) {
@@ -1486,7 +1565,7 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
   __syncthreads();
   TTR_ESTAMP();
 #ifdef TTR_EIGH_STAMPS
-  if (dbg && bt == 0 && tid == 0) { dbg[dbgi++] = total_iter; dbg[dbgi++] = nrot_dbg; dbg[dbgi++] = qlrec_dbg; dbg[dbgi++] = 0; }
+  if (dbg && bt == p.stamp_block && tid == 0) { dbg[dbgi++] = total_iter; dbg[dbgi++] = nrot_dbg; dbg[dbgi++] = qlrec_dbg; dbg[dbgi++] = 0; }
 #endif
 
   // ---- 4. epilogue: un-scale, clamp / sqrt / sort, permuted write, rank rule (round.py:118-158)
@@ -1558,8 +1637,10 @@ __global__ __launch_bounds__(2 * kWave, (MINW > 0 ? MINW : (sizeof(T) == 4 && NM
   }
 }
 
-static size_t eigh_tridiag_lds_bytes(size_t elem, int64_t n) {  // A, 3 pad, 408 scratch, d / e (66 each), tau, T_b, 8 control words, d / e^2 of the Sturm counts (2 x 64, 16-byte aligned)
-  return (((size_t)n * (n + 1) + 3 + 408 + 66 * 2 + 64 + 16 * 17 + 8 + 4 + 128) * elem + 15) & ~size_t(15);
+// A, 3 pad, 408 scratch, d / e (66 each), tau, T_b, 8 control words, d / e^2 of the Sturm counts (2 x 64, 16-byte aligned); the lean
+// 32-row instance: and the pivots D+ / D- of its twisted factorisations (2 x 32 x 32)
+static size_t eigh_tridiag_lds_bytes(size_t elem, int64_t n, bool lean = false) {
+  return (((size_t)n * (n + 1) + 3 + 408 + 66 * 2 + 64 + 16 * 17 + 8 + 4 + 128 + (lean ? 2 * 32 * 32 : 0)) * elem + 15) & ~size_t(15);
 }
 
 
@@ -1596,7 +1677,7 @@ int g_rank_noise_c = 1;  // ttr_debug_set_knob(TTR_KNOB_RANK_NOISE_FLOOR, c): se
 int g_jacobi_live_wave = 0;
 int g_eigh_big_occ = 0;   // ttr_debug_set_knob(TTR_KNOB_EIGH_BIG_OCC): waves per SIMD the 64-row top-r instance is built for (0 = 4)
 int g_eigh_small = 2;   // ttr_debug_set_knob(TTR_KNOB_EIGH_SMALL): 0 = no separate 32-row launch, 1 = the 32-row instance, 2 (default) / 3 = and its
-                        // large fp32 top-r launches at three / four waves per SIMD (A/B)
+                        // large fp32 top-r launches in the lean 128-register build at four waves per SIMD
 template <typename T>
 static int eigh_typed(int dtype, int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts,
                       int64_t stride_gpart, void* V,
@@ -1682,8 +1763,10 @@ int eigh_dispatch(int dtype, int64_t n, int64_t batch, const void* G, int64_t ld
 
 // pass 1 of a batch-mode bond, n <= 64: the r largest eigenpairs (flat[b] = 1) or the full QL decomposition (flat[b] = 0) per item
 #ifdef TTR_EIGH_STAMPS
-static void* g_eigh_stamps = nullptr;   // diagnostics build: cycle stamps of matrix 0 of the next ttr_eigh_top launches (>= 64 int64)
+static void* g_eigh_stamps = nullptr;   // diagnostics build: cycle stamps of one block of the next ttr_eigh_top launches (>= 64 int64)
+static long long g_eigh_stamp_block = 0;
 extern "C" void ttr_debug_set_eigh_stamps(void* p) { g_eigh_stamps = p; }
+extern "C" void ttr_debug_set_eigh_stamp_block(long long b) { g_eigh_stamp_block = b; }
 #endif
 template <typename T>
 static int eigh_top_typed(int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts, int64_t stride_gpart,
@@ -1699,19 +1782,23 @@ static int eigh_top_typed(int64_t n, int64_t batch, const void* G, int64_t ldg, 
   p.eig_mode = TTR_EIG_RAW;
 #ifdef TTR_EIGH_STAMPS
   p.ws = (T*)g_eigh_stamps;
+  p.stamp_block = g_eigh_stamp_block;
 #endif
   ProfScope prof(TTR_PROF_EIGH, stream);
   if (n == 64 && g_eigh_small) {   // zero-tail items first, in the 32-row instance (see the kernel)
-    // Large fp32 launches go through a build capped at 168 VGPRs (TTR_KNOB_EIGH_SMALL = 2, the default; 3: 128): the instance needs
-    // 210 registers, i.e. two waves per SIMD = FOUR matrices per CU at a time, each of them latency-bound -- three waves per SIMD
-    // with 44 spilled registers (four: 124) is the faster trade from 1024 matrices per launch on (B = 4096: eigh 3.75 -> 3.13 ms
-    // per step of event time, the step 24.91 -> 24.77 ms, bit-identical results: profiles/r05_eigh_occ_ab.txt); a single matrix
-    // keeps the spill-free build.
-    if (sizeof(T) == 4 && g_eigh_small == 2 && batch >= 1024)
-      hipLaunchKernelGGL((eigh_tridiag_kernel<T, true, 32, 3>), dim3((unsigned)batch), dim3(2 * kWave), eigh_tridiag_lds_bytes(sizeof(T), 32), stream, p);
-    else if (sizeof(T) == 4 && g_eigh_small == 3 && batch >= 1024)
-      hipLaunchKernelGGL((eigh_tridiag_kernel<T, true, 32, 4>), dim3((unsigned)batch), dim3(2 * kWave), eigh_tridiag_lds_bytes(sizeof(T), 32), stream, p);
-    else
+    // Large fp32 launches go through the lean build (TTR_KNOB_EIGH_SMALL = 2, the default, and 3): the unrolled instance takes
+    // 208 registers, i.e. two waves per SIMD = FOUR matrices per CU at a time, each of them latency-bound.  The lean one keeps the
+    // pivots of the twisted factorisation in LDS and runs its recurrences as loops (see `select`): 108 registers, no scratch,
+    // four waves per SIMD = EIGHT matrices per CU, so 4096 matrices are exactly two rounds, with bit-identical results.  It
+    // replaces the builds of the unrolled instance under a register cap (168: 42 spilled registers, three waves; 128: 125 spilled),
+    // profiles/r05_eigh_occ_ab.txt and profiles/HISTORY.md.  Smaller launches and fp64 keep the unrolled instance.
+    bool lean = false;
+    if constexpr (sizeof(T) == 4) {
+      lean = (g_eigh_small == 2 || g_eigh_small == 3) && batch >= 1024;
+      if (lean)
+        hipLaunchKernelGGL((eigh_tridiag_kernel<T, true, 32, 4>), dim3((unsigned)batch), dim3(2 * kWave), eigh_tridiag_lds_bytes(sizeof(T), 32, true), stream, p);
+    }
+    if (!lean)
       hipLaunchKernelGGL((eigh_tridiag_kernel<T, true, 32>), dim3((unsigned)batch), dim3(2 * kWave), eigh_tridiag_lds_bytes(sizeof(T), 32), stream, p);
     TTR_HIP_CHECK(hipGetLastError());
     p.top_pre = 1;
