@@ -53,7 +53,7 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict and ttr_mode_sandwich were ADDED under 17: no existing signature changed, and a library without the
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich and ttr_sample_max_rank / ttr_sample_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
@@ -1060,6 +1060,46 @@ int64_t ttr_minimize_workspace_bytes(int dtype, int64_t M);
 int ttr_minimize_step(int dtype, void* e, int64_t Ra, int64_t I, int64_t Rb, const void* lset, int64_t ld_lset, int64_t nl,
                       const void* rset, int64_t ld_rset, int64_t nr, void* best, void* pos, void* flags, void* workspace,
                       int64_t workspace_bytes, void* stream);
+
+/*
+ * One mode of sampling from a train read as an unnormalised mass function (added under ABI 17; tools.py:362-407 `sample`, which
+ * forms the P x I matrix lefts @ fiber and passes over it about ten times): one launch per mode, the matrix
+ * never exists in global memory and there is no workspace.
+ *
+ * ttr_sample_step     per sample p < P, with q[i] = |sum_a L[p, a] fiber[a, i]| computed in the dtype on the matrix cores and the
+ *                     running sum c_i = q[0] + .. + q[i] and T = c_{I-1} in fp64 whatever the dtype:
+ *                       X[p stride_x] = the smallest i with c_i > u[p stride_u] T (compared in fp64); where the rounding of u T
+ *                                       leaves none, the last i with q[i] > 0
+ *                       Lnew[p, :]    = (L[p, :] @ core[:, x, :]) / T, the product an fma chain in the dtype, the quotient in
+ *                                       fp64, rounded once at the store; not computed when Lnew is NULL (the last mode)
+ *
+ * `L` [P, r] with the row stride ldl (elements; unit column stride), `fiber` [r, I] contiguous (the core times the right vector
+ * of the next mode: an input, as in ttr_accept_count), `core` [r, I, rn] with the element strides core_strides[3] (a HOST array;
+ * the last must be 1, the others >= 0, the stride of an extent-1 axis is free), `u` fp64 thresholds in [0, 1), `X` int64,
+ * `Lnew` [P, rn] with the row stride ldn.  `flag` is one int32 device word, zeroed by the caller before the first mode and ORed
+ * only where a check of a sample fails: TTR_SAMPLE_ZERO_TOTAL (T == 0), TTR_SAMPLE_NONFINITE (T not finite),
+ * TTR_SAMPLE_BAD_THRESHOLD (u outside [0, 1) or NaN).  A flagged sample stores X = -1 and a zero row of Lnew.
+ * A workgroup owns TTR_SAMPLE_TILE_F32 / _F64 samples (a wave a quarter of them) and forms q in blocks of TTR_SAMPLE_BLOCK_F32 /
+ * _F64 columns of fiber; the running sum is sequential over the columns in segments of 16 (fp32) / 4 (fp64): inside a segment
+ * from the segment's own partial sums, from segment to segment by their totals.  Every store is indexed by the sample's own p;
+ * the only data-dependent address is the LOAD of core[:, x, :] with 0 <= x < I.  X[p] and Lnew[p, :] depend on the inputs of
+ * sample p alone: not on P, on the other samples or on its place in a tile; the same call gives the same bits.
+ * ttr_sample_max_rank(): the largest r and rn.
+ * Before any device call: TTR_E_INVALID for a bad dtype, P < 0, an extent < 1, a rank above the limit, a null pointer (Lnew
+ * excepted); TTR_E_UNSUPPORTED for a core whose last stride is not 1 or with a negative stride, ldl < r, ldn < rn, stride_u or
+ * stride_x < 1, I or P beyond 2^31 - 64 columns / 2^35 samples.  P == 0 returns at once.  Profiling kind: TTR_PROF_MISC.
+ */
+#define TTR_SAMPLE_ZERO_TOTAL 1
+#define TTR_SAMPLE_NONFINITE 2
+#define TTR_SAMPLE_BAD_THRESHOLD 4
+#define TTR_SAMPLE_TILE_F32 128
+#define TTR_SAMPLE_TILE_F64 64
+#define TTR_SAMPLE_BLOCK_F32 32
+#define TTR_SAMPLE_BLOCK_F64 16
+int ttr_sample_max_rank(void);
+int ttr_sample_step(int dtype, int64_t P, int64_t r, int64_t I, int64_t rn, const void* L, int64_t ldl, const void* fiber,
+                    const void* core, const int64_t* core_strides, const void* u, int64_t stride_u, void* X, int64_t stride_x,
+                    void* Lnew, int64_t ldn, void* flag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,8 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ``tools.py`` and ``ops.py``: ``tn.squeeze``, ``tn.unsqueeze``, ``tn.unbind``, ``tn.cat``, ``tn.transpose``, ``tn.flip``, ``tn.pad``,
 ``tn.ttm``, ``tn.generate_basis`` and ``tn.cumsum`` (marginalising a mode is ``tn.squeeze(tn.ttm(t, weights, dim))``; there is no
 ``tn.sum`` / ``tn.mean``), and the variance-based sensitivity analysis of ``anova.py``: ``tn.anova_decomposition``,
-``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``.
+``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``,
+and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``.
 """
 
 from .tools import *  # noqa: F401,F403

@@ -1534,3 +1534,46 @@ def accept_expand(L: torch.Tensor, core: torch.Tensor, C: torch.Tensor, childoff
     _call("ttr_accept_expand", dt, P, r, I, rn, K, N, int(mu), S, L.data_ptr(), core.data_ptr(), C.data_ptr(), childoff.data_ptr(),
           cnt.data_ptr(), idx.data_ptr(), _ptr(Lnew), offnew.data_ptr(), cntnew.data_ptr(), Xs.data_ptr(), flag.data_ptr())
     return Lnew, offnew, cntnew
+
+
+def sample_max_rank() -> int:
+    """ttr_sample_max_rank: the largest rank ttr_sample_step takes."""
+    return int(lib().ttr_sample_max_rank())
+
+
+def sample_tile(dt: torch.dtype) -> Tuple[int, int]:
+    """(S, B) of ttr_sample_step in this dtype: the samples a workgroup owns and the columns of fiber per block
+    (TTR_SAMPLE_TILE_* / TTR_SAMPLE_BLOCK_* of the header)."""
+    return (SAMPLE_TILE_F32, SAMPLE_BLOCK_F32) if dtype_code(dt) == F32 else (SAMPLE_TILE_F64, SAMPLE_BLOCK_F64)
+
+
+@_on_device
+def sample_step(L: torch.Tensor, fiber: torch.Tensor, core: torch.Tensor, u: torch.Tensor, x: torch.Tensor, flag: torch.Tensor,
+                Lnew: Optional[torch.Tensor] = None) -> None:
+    """ttr_sample_step: one mode of the sampling sweep for the P rows of L [P, r] (unit column stride, any row stride >= r):
+    x[p] (int64 [P], any stride: a column of Xs) = the index drawn with the threshold u[p] (fp64 [P], any stride) from
+    q = |L[p, :] @ fiber| (fiber [r, I] contiguous), and Lnew[p, :] = (L[p, :] @ core[:, x[p], :]) / sum q when ``Lnew``
+    ([P, r'], unit column stride) is given.  ``core`` [r, I, r'] is taken with its own strides (the entry refuses what it does
+    not take: NotImplementedError).  ``flag`` (int32 [1]) is ORed with SAMPLE_* bits; nothing is read back.  ValueError for a
+    rank above sample_max_rank()."""
+    dt = dtype_code(core.dtype)
+    if L.dim() != 2 or fiber.dim() != 2 or core.dim() != 3 or u.dim() != 1 or x.dim() != 1:
+        raise ValueError("sample_step: expected L [P, r], fiber [r, I], core [r, I, r'], u [P] and x [P]")
+    P, r = L.shape
+    I, rn = core.shape[1], core.shape[2]
+    tensors = [L, fiber, core, u, x, flag] + ([Lnew] if Lnew is not None else [])
+    if not all(t.is_cuda and t.device == core.device for t in tensors):
+        raise ValueError("sample_step: every operand must be on the core's device")
+    if not (L.dtype == core.dtype and fiber.dtype == core.dtype and tuple(fiber.shape) == (r, I) and fiber.is_contiguous()
+            and core.shape[0] == r and (r == 1 or L.stride(1) == 1)):
+        raise ValueError("sample_step: L [P, r] (unit column stride) and a contiguous fiber [r, I] of the core's dtype are needed")
+    if not (u.dtype == torch.float64 and u.shape[0] == P and x.dtype == torch.int64 and x.shape[0] == P):
+        raise ValueError("sample_step: u must be fp64 [P] and x int64 [P]")
+    if not (flag.dtype == torch.int32 and flag.numel() == 1):
+        raise ValueError("sample_step: flag must be one int32 word")
+    if Lnew is not None and not (Lnew.dtype == core.dtype and tuple(Lnew.shape) == (P, rn) and (rn == 1 or Lnew.stride(1) == 1)):
+        raise ValueError("sample_step: Lnew must be [P, r'] of the core's dtype with unit column stride")
+    cs = (c_int64 * 3)(*[int(s) for s in core.stride()])
+    _call("ttr_sample_step", dt, P, r, I, rn, L.data_ptr(), int(L.stride(0)) if P > 1 else r, fiber.data_ptr(), core.data_ptr(), cs,
+          u.data_ptr(), int(u.stride(0)) if P > 1 else 1, x.data_ptr(), int(x.stride(0)) if P > 1 else 1, _ptr(Lnew),
+          (int(Lnew.stride(0)) if P > 1 else rn) if Lnew is not None else rn, flag.data_ptr())

@@ -2205,3 +2205,21 @@ def accept_count(L: torch.Tensor, fiber: torch.Tensor) -> torch.Tensor:
 def accept_expand(L, core, C, childoff, cnt, idx, Xs, mu, flag, last):
     """The listed children of one frontier through one core (ttr_accept_expand): (Lnew, offnew, cntnew); fills Xs[:, mu]."""
     return _hip.accept_expand(L.contiguous(), core.contiguous(), C, childoff.contiguous(), cnt, idx, Xs, mu, flag, last)
+
+
+# ---------------------------------------------------------------------------------------------- sampling (tools.py:362-407)
+def sample_max_rank() -> int:
+    return _hip.sample_max_rank()
+
+
+def sample_fibers(cores):
+    """fibers[mu] = core_mu x_3 right_{mu+1} ([r_mu, I_mu], the cores' dtype; one ttr_gemm each), the right vectors divided by
+    their largest magnitude.  Nothing is read back."""
+    return _hostops._sample_fibers(cores, lambda A, v: _hip.gemm(A[None], v.reshape(1, -1, 1)).reshape(-1))
+
+
+def sample_step(L, fiber, core, u, x, flag, last):
+    """One mode of the sampling sweep (ttr_sample_step): fills ``x``, ORs ``flag``, returns Lnew [P, r'] or None when ``last``."""
+    Lnew = None if last else torch.empty((L.shape[0], core.shape[2]), dtype=core.dtype, device=core.device)
+    _hip.sample_step(L, fiber, core, u, x, flag, Lnew)
+    return Lnew

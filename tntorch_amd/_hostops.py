@@ -836,3 +836,59 @@ def accept_expand(L, core, C, childoff, cnt, idx, Xs, mu, flag, last):
         k = (torch.searchsorted(offnew, rows, right=True) - 1).clamp(0, K - 1)   # the last slot with offnew[k] <= s
         Xs[:, mu] = i[k]
     return Lnew, offnew, cntnew
+
+
+# ---------------------------------------------------------------------------------------------- sampling (tools.py:362-407)
+SAMPLE_ZERO_TOTAL, SAMPLE_NONFINITE, SAMPLE_BAD_THRESHOLD = 1, 2, 4   # include/ttround_hip.h: TTR_SAMPLE_*
+
+
+def sample_max_rank():
+    """The host mirror has no rank limit."""
+    return None
+
+
+def _sample_fibers(cores, matvec):
+    right = torch.ones((cores[-1].shape[2],), dtype=cores[0].dtype, device=cores[0].device)
+    fibers = []
+    for c in reversed(cores):
+        r, I, rn = c.shape
+        f = matvec(c.reshape(r * I, rn), right).reshape(r, I)
+        fibers.append(f)
+        right = f.sum(dim=1)
+        # any positive scale of a right vector cancels in the comparison with u T; a zero vector stays zero (and is flagged)
+        right = right / right.abs().max().clamp_min(torch.finfo(right.dtype).tiny)
+    return fibers[::-1]
+
+
+def sample_fibers(cores):
+    """fibers[mu] = core_mu x_3 right_{mu+1} ([r_mu, I_mu], the cores' dtype), right_N = 1 and right_mu = sum_i fibers[mu][:, i]
+    divided by its largest magnitude."""
+    return _sample_fibers(cores, lambda A, v: A @ v)
+
+
+def sample_step(L, fiber, core, u, x, flag, last):
+    """Mirror of ttr_sample_step with the same definition: q = |L @ fiber| in the dtype, the running sum c and T in fp64,
+    x[p] = the first i with c_i > u[p] T[p] (where rounding leaves none, the last i with q > 0), Lnew = (L @ core[:, x, :]) / T
+    rounded once.  Fills ``x`` (a column of Xs), ORs ``flag`` (int32 [1]); a flagged sample gets x = -1 and a zero row.  Returns
+    Lnew [P, r'] or None when ``last``."""
+    P, I = L.shape[0], fiber.shape[1]
+    q = (L @ fiber).abs().double()
+    c = torch.cumsum(q, dim=1)
+    T = c[:, -1]
+    first = (c <= (u * T)[:, None]).sum(dim=1)             # c is non-decreasing: the number of c_i <= u T
+    lastpos = ((q > 0) * torch.arange(1, I + 1, device=q.device)).amax(dim=1) - 1
+    xi = torch.where(first < I, first, lastpos)
+    bad_u = ~((u >= 0) & (u < 1))
+    zero = T == 0
+    nonfinite = ~torch.isfinite(T)
+    flagged = bad_u | zero | nonfinite | (xi < 0)
+    bits = ((SAMPLE_BAD_THRESHOLD if bool(bad_u.any()) else 0) | (SAMPLE_ZERO_TOTAL if bool(zero.any()) else 0)
+            | (SAMPLE_NONFINITE if bool(nonfinite.any()) else 0))
+    flag |= bits
+    xi = torch.where(flagged, torch.full_like(xi, -1), xi)
+    x.copy_(xi)
+    if last:
+        return None
+    G = core[:, xi.clamp_min(0), :]                                     # [r, P, r']
+    Lnew = (torch.einsum("pa,apb->pb", L, G).double() / T[:, None]).to(L.dtype)
+    return torch.where(flagged[:, None], torch.zeros_like(Lnew), Lnew)

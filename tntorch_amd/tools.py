@@ -4,8 +4,8 @@ path -- and the rounding tree.
 Mirror of ``tntorch/tools.py``: the array tools (tools.py:14-208: ``squeeze``, ``unsqueeze``, ``cat``, ``transpose``, ``meshgrid``,
 ``flip``, ``unbind``), the unfoldings (tools.py:211-258), ``ttm`` (tools.py:266-325), ``mask`` (tools.py:333-359),
 ``generate_basis`` (tools.py:427-457), ``reduce`` (tools.py:460-512), ``pad`` (tools.py:515-576) and ``convolve``
-(tools.py:579-647), with the names, arguments and results of the reference; what differs is listed in each docstring.  ``sample``
-and ``hash`` are out of scope.  The array tools follow the input's device and dtype (fp32 or fp64) and never modify their inputs;
+(tools.py:579-647), and ``sample`` (tools.py:362-407), with the names, arguments and results of the reference; what differs is
+listed in each docstring.  ``hash`` is out of scope.  The array tools follow the input's device and dtype (fp32 or fp64) and never modify their inputs;
 on device tensors a matrix factor goes through the MFMA GEMM (``mode_mul``), a vector factor through ``ttr_mode_reduce``, and
 everything else is slicing and copies of cores.
 
@@ -14,13 +14,14 @@ unfolding has row index ``r0*I + i`` and its right unfolding column index ``i*R1
 exactly the addressing the HIP kernels use (no data movement on either side).
 """
 
+import operator
 import time
 
 import numpy as np
 import torch
 
 __all__ = ["meshgrid", "unfolding", "right_unfolding", "left_unfolding", "reduce", "shift_mode", "convolve", "mask", "squeeze",
-           "unsqueeze", "cat", "transpose", "flip", "unbind", "ttm", "generate_basis", "pad"]
+           "unsqueeze", "cat", "transpose", "flip", "unbind", "ttm", "generate_basis", "pad", "sample"]
 
 
 def meshgrid(*axes, batch=False):
@@ -643,3 +644,82 @@ def pad(t, shape, dim=None, fill_value=0):
         fill.append(core.contiguous())
     fill[0] = ops_for(fill[0]).scale(fill[0], fill_value)
     return result + Tensor(fill)
+
+
+def _sample_from_thresholds(t, U):
+    """The sweep of :func:`sample` for given thresholds ``U`` (fp64 ``[P, N]`` on ``t``'s device, entries in ``[0, 1)``): sample
+    ``p`` takes at mode ``mu`` the smallest index whose running conditional mass exceeds ``U[p, mu]`` times the total."""
+    from .automata import _cores3
+
+    return _sample_sweep(_cores3(t, "sample"), U)
+
+
+def _sample_sweep(cores, U):
+    from . import _hostops
+    from ._dispatch import ops_for
+
+    ops = ops_for(cores[0])
+    dev, N = cores[0].device, len(cores)
+    if not (isinstance(U, torch.Tensor) and U.dim() == 2 and U.shape[1] == N and U.dtype == torch.float64 and U.device == dev):
+        raise ValueError("sample: the thresholds must be an fp64 [P, {}] tensor on the tensor's device".format(N))
+    limit = ops.sample_max_rank()
+    rmax = max(max(c.shape[0], c.shape[2]) for c in cores)
+    if limit is not None and rmax > limit:
+        raise ValueError("sample: rank {} is above the limit of {} (ttr_sample_max_rank)".format(rmax, limit))
+    P = U.shape[0]
+    Xs = torch.empty((P, N), dtype=torch.int64, device=dev)
+    if P == 0:
+        return Xs
+    fibers = ops.sample_fibers(cores)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    L = torch.ones((P, cores[0].shape[0]), dtype=cores[0].dtype, device=dev)
+    for mu in range(N):
+        L = ops.sample_step(L, fibers[mu], cores[mu], U[:, mu], Xs[:, mu], flag, mu == N - 1)
+    word = int(flag.item())                                             # (the one readback of a call)
+    if word != 0:
+        raise ValueError("sample: {} (flag word {})".format("; ".join(
+            text for bit, text in ((_hostops.SAMPLE_ZERO_TOTAL, "a sample met a conditional distribution of zero total mass (the zero tensor, or a "
+                                                                    "prefix whose left vector annihilates the next fiber)"),
+                                   (_hostops.SAMPLE_NONFINITE, "a conditional total is not finite (NaN or infinity in the cores)"),
+                                   (_hostops.SAMPLE_BAD_THRESHOLD, "a threshold lies outside [0, 1)")) if word & bit), word))
+    return Xs
+
+
+def sample(t, P=1, seed=None):
+    """Draw ``P`` index vectors, with replacement, from the distribution whose unnormalised mass function is ``t``
+    (tools.py:362-407).  The conditional marginal of a mode given the earlier indices is taken in absolute value, as the
+    reference takes it; ``t`` does not have to sum to 1.
+
+    What differs from the reference: the result is int64 and lives on ``t``'s device (the reference returns a float32 CPU
+    matrix); the thresholds are compared with ``u T`` instead of normalising each row, the left vectors are divided by their
+    total ``T`` and the right vectors by their largest magnitude (scales that cancel; without them fp32 underflows after a few
+    dozen modes); where rounding leaves no index above the threshold the last index of positive mass is taken; a conditional
+    distribution of zero or non-finite total raises ``ValueError`` (the reference divides by zero).  On device tensors each mode is
+    one launch of ``ttr_sample_step``: the ``P x I`` matrix of the reference never exists, and one word is read back at the end.
+
+    :param t: a :class:`Tensor` (Tucker factors are contracted in first; ``t`` is not modified)
+    :param P: how many samples to draw (default: 1)
+    :param seed: an int reproduces the reference's thresholds (``np.random.default_rng(seed)``, ``rng.random(P)`` once per mode,
+        drawn on the host and uploaded once); ``None`` draws ``torch.rand((P, N), dtype=torch.float64, device=...)`` on the device
+
+    :return: an int64 matrix ``[P, N]`` on ``t``'s device
+
+    Raises ValueError for batched tensors, for ``P < 0`` or a non-integer ``P``, for a rank above ``ttr_sample_max_rank()`` on
+    device tensors and for a zero or non-finite conditional total; NotImplementedError for CP cores.
+    """
+    from .automata import _cores3
+
+    try:
+        P = operator.index(P)
+    except TypeError:
+        raise ValueError("sample: P must be a non-negative integer, got {!r}".format(P)) from None
+    if P < 0:
+        raise ValueError("sample: P must be a non-negative integer, got {}".format(P))
+    cores = _cores3(t, "sample")
+    dev, N = cores[0].device, len(cores)
+    if seed is None:
+        U = torch.rand((P, N), dtype=torch.float64, device=dev)
+    else:
+        rng = np.random.default_rng(seed=seed)
+        U = torch.from_numpy(np.stack([rng.random(P) for _ in range(N)], axis=1)).to(dev)
+    return _sample_sweep(cores, U)
