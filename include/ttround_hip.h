@@ -53,7 +53,7 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
-   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich and ttr_sample_max_rank / ttr_sample_step were ADDED under 17: no existing signature changed, and a library without the
+   round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
@@ -1100,6 +1100,42 @@ int ttr_sample_max_rank(void);
 int ttr_sample_step(int dtype, int64_t P, int64_t r, int64_t I, int64_t rn, const void* L, int64_t ldl, const void* fiber,
                     const void* core, const int64_t* core_strides, const void* u, int64_t stride_u, void* X, int64_t stride_x,
                     void* Lnew, int64_t ldn, void* flag, void* stream);
+
+/*
+ * One step of the product of a TT-matrix or a CP-matrix with a dense batch (added under ABI 17; matrix.py:420-443 `tt_multiply` and
+ * 446-468 `cp_multiply`, chains of d einsum calls, each a permuted copy of the running intermediate and a GEMM).
+ * With the reference's index order the row-major output of step k IS the input of step k + 1: Y [D, O, S] read as
+ * [I', D', S] with D = I' D'' and D' = (D'', O).  Nothing is permuted, padded or copied, and there is no workspace.
+ *
+ * ttr_ttm_step   Y[dd, o, s] = sum_i sum_r X[i, dd, r] G[r, i, o, s].  `X` [I, D, R], `G` [R, I, O, S] (a TTMatrix core) and `Y`
+ *                [D, O, S] are contiguous; the element strides of X (3) and of G (4) are passed as HOST arrays and checked as
+ *                ttr_core_matvec checks them: TTR_E_UNSUPPORTED before a byte is read, the stride of an extent-1 axis is free.
+ *                A GEMM with M = D, N = O S and K = I R on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 (operands and
+ *                accumulators in the dtype) whose K index k = i R + r has two strides in X: X is read in place, in runs of equal i,
+ *                so a quad of k that straddles two i (every R that is no multiple of 4) takes its halves from their own
+ *                addresses.  A workgroup owns TTR_TTM_TILE_M x TTR_TTM_TILE_N of Y and walks K in tiles of TTR_TTM_TILE_K
+ *                through LDS; column tiles of 16 past N and quads of k past K are not multiplied (N < 16: the last step; K < 4:
+ *                the first step of a small mode).  Any I, D, R, O, S >= 1 with D, I R and O S at most 2^31 - 1 (beyond that
+ *                TTR_E_UNSUPPORTED): no rank limit, 64-bit element offsets.  No atomics, no split of K across workgroups: every
+ *                element of Y is one accumulation chain in increasing k, its order fixed by the five extents and the dtype; the
+ *                same call gives the same bits.  Profiling kind: TTR_PROF_GEMM.
+ * ttr_cpm_step   Y[dd, o, r] = sum_i X[i, dd, r] C[i, o, r] (x_has_rank = 1) or sum_i X[i, dd] C[i, o, r] (x_has_rank = 0: the
+ *                first step, X broadcast over r).  `X` [I, D, R] or [I, D], `C` [I, O, R] (a CPMatrix core), `Y` [D, O, R]: all
+ *                contiguous.  A streaming kernel on the vector ALUs: 16-byte accesses along r where R is a multiple of 16 bytes of
+ *                elements and the pointers are 16-byte aligned, else scalar ones with the same arithmetic (the bits do not depend
+ *                on where the buffers lie); the sum over i is an fma chain from 0 in increasing i.  The final sum over r of
+ *                `cp_multiply` is ttr_mode_reduce (R = D O, I = rank, C = 1).  Profiling kind: TTR_PROF_MISC.
+ * Before any launch, with Y untouched: TTR_E_INVALID for a bad dtype, an extent < 1, an x_has_rank other than 0 / 1, a null
+ * pointer or a Y that is one of the inputs; TTR_E_UNSUPPORTED for strides other than the contiguous ones and for an operand of
+ * 2^57 elements or more.
+ */
+#define TTR_TTM_TILE_M 64
+#define TTR_TTM_TILE_N 64
+#define TTR_TTM_TILE_K 32
+int ttr_ttm_step(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S, const void* X, const int64_t* x_strides,
+                 const void* G, const int64_t* g_strides, void* Y, void* stream);
+int ttr_cpm_step(int dtype, int64_t I, int64_t D, int64_t O, int64_t R, int x_has_rank, const void* X, const void* C, void* Y,
+                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ``tn.ttm``, ``tn.generate_basis`` and ``tn.cumsum`` (marginalising a mode is ``tn.squeeze(tn.ttm(t, weights, dim))``; there is no
 ``tn.sum`` / ``tn.mean``), and the variance-based sensitivity analysis of ``anova.py``: ``tn.anova_decomposition``,
 ``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``,
-and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``.
+and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``, and the matrix formats of
+``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``.
 """
 
 from .tools import *  # noqa: F401,F403

@@ -1577,3 +1577,40 @@ def sample_step(L: torch.Tensor, fiber: torch.Tensor, core: torch.Tensor, u: tor
     _call("ttr_sample_step", dt, P, r, I, rn, L.data_ptr(), int(L.stride(0)) if P > 1 else r, fiber.data_ptr(), core.data_ptr(), cs,
           u.data_ptr(), int(u.stride(0)) if P > 1 else 1, x.data_ptr(), int(x.stride(0)) if P > 1 else 1, _ptr(Lnew),
           (int(Lnew.stride(0)) if P > 1 else rn) if Lnew is not None else rn, flag.data_ptr())
+
+
+@_on_device
+def ttm_step(X: torch.Tensor, G: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ttm_step: X [I, D, R], G [R, I, O, S] (a TTMatrix core) -> Y [D, O, S], Y[dd, o, s] = sum_i sum_r X[i, dd, r] G[r, i, o, s].
+    The operands are passed with the strides they have: the library refuses anything but contiguous ones (NotImplementedError).
+    ``out``: a contiguous tensor of D O S elements that receives the result (its shape is not looked at: the caller reads it as
+    the next step's X); a fresh [D, O, S] tensor when None."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and G.dim() == 4 and G.dtype == X.dtype and G.device == X.device
+    I, D, R = X.shape
+    assert G.shape[0] == R and G.shape[1] == I
+    O, S = G.shape[2], G.shape[3]
+    if out is None:
+        out = torch.empty((D, O, S), dtype=X.dtype, device=X.device)
+    assert out.numel() == D * O * S and out.is_contiguous() and out.dtype == X.dtype and out.device == X.device
+    _call("ttr_ttm_step", dt, I, D, R, O, S, X.data_ptr(), _i64(X.stride()), G.data_ptr(), _i64(G.stride()), out.data_ptr())
+    return out
+
+
+@_on_device
+def cpm_step(X: torch.Tensor, C: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_cpm_step: X [I, D, R] (or [I, D]: the first step, broadcast over r), C [I, O, R] (a CPMatrix core) -> Y [D, O, R],
+    Y[dd, o, r] = sum_i X[i, dd, r] C[i, o, r].  The entry takes contiguous operands only (it has no stride arguments), so
+    anything else is refused here (ValueError).  ``out``: a contiguous tensor of D O R elements; a fresh [D, O, R] tensor when None."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() in (2, 3) and C.dim() == 3 and C.dtype == X.dtype and C.device == X.device
+    I, O, R = C.shape
+    D = X.shape[1]
+    assert X.shape[0] == I and (X.dim() == 2 or X.shape[2] == R)
+    if not (X.is_contiguous() and C.is_contiguous()):
+        raise ValueError("cpm_step: X and C must be contiguous")
+    if out is None:
+        out = torch.empty((D, O, R), dtype=X.dtype, device=X.device)
+    assert out.numel() == D * O * R and out.is_contiguous() and out.dtype == X.dtype and out.device == X.device
+    _call("ttr_cpm_step", dt, I, D, O, R, int(X.dim() == 3), X.data_ptr(), C.data_ptr(), out.data_ptr())
+    return out

@@ -2223,3 +2223,28 @@ def sample_step(L, fiber, core, u, x, flag, last):
     Lnew = None if last else torch.empty((L.shape[0], core.shape[2]), dtype=core.dtype, device=core.device)
     _hip.sample_step(L, fiber, core, u, x, flag, Lnew)
     return Lnew
+
+
+# ---------------------------------------------------------------------------------------------- TT / CP matrix products (matrix.py:420-468)
+def tt_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.Tensor:
+    """x2d [b, prod I_k] times the TT-matrix with the cores G_k [r_k, I_k, O_k, r_{k+1}] -> [b, prod O_k]: one ttr_ttm_step per
+    core.  The transposed copy of x2d at entry is the only copy: the output of a step is the next step's input as it lies, and
+    only a step's input and output are alive at a time."""
+    b = x2d.shape[0]
+    X = x2d.t().contiguous()
+    for G in cores:
+        R, I = G.shape[0], G.shape[1]
+        X = _hip.ttm_step(X.view(I, -1, R), G.contiguous())
+    return X.view(b, -1)
+
+
+def cp_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.Tensor:
+    """x2d [b, prod I_k] times the CP-matrix with the cores C_k [I_k, O_k, R] -> [b, prod O_k]: one ttr_cpm_step per core, then
+    the sum over the rank by ttr_mode_reduce."""
+    b = x2d.shape[0]
+    X = x2d.t().contiguous()
+    for k, C in enumerate(cores):
+        I, R = C.shape[0], C.shape[2]
+        X = _hip.cpm_step(X.view(I, -1) if k == 0 else X.view(I, -1, R), C.contiguous())
+    R = cores[-1].shape[2]
+    return _hip.mode_reduce(X.view(-1, R, 1)).view(b, -1)

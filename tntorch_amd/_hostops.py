@@ -892,3 +892,28 @@ def sample_step(L, fiber, core, u, x, flag, last):
     G = core[:, xi.clamp_min(0), :]                                     # [r, P, r']
     Lnew = (torch.einsum("pa,apb->pb", L, G).double() / T[:, None]).to(L.dtype)
     return torch.where(flagged[:, None], torch.zeros_like(Lnew), Lnew)
+
+
+# ---------------------------------------------------------------------------------------------- TT / CP matrix products (matrix.py:420-468)
+def tt_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.Tensor:
+    """x2d [b, prod I_k] times the TT-matrix with the cores G_k [r_k, I_k, O_k, r_{k+1}] (r_0 = r_d = 1) -> [b, prod O_k]: the
+    chain of ttr_ttm_step in torch ops.  X_0 = x2d^T read as [I_0, D_0, 1]; step k contracts (i, r) of X_k [I_k, D_k, r_k] with
+    G_k and its output [D_k, O_k, r_{k+1}], row-major, is X_{k+1} [I_{k+1}, D_{k+1}, r_{k+1}]: a reshape, never a copy."""
+    b = x2d.shape[0]
+    X = x2d.t().contiguous()
+    for G in cores:
+        R, I = G.shape[0], G.shape[1]
+        X = torch.einsum("idr,rios->dos", X.reshape(I, -1, R), G)
+    return X.reshape(b, -1)
+
+
+def cp_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.Tensor:
+    """x2d [b, prod I_k] times the CP-matrix with the cores C_k [I_k, O_k, R] -> [b, prod O_k]: the chain of ttr_cpm_step in
+    torch ops (the rank index is carried, step 0 broadcasts X_0 over it), then the sum over the rank."""
+    b = x2d.shape[0]
+    X = x2d.t().contiguous()
+    for k, C in enumerate(cores):
+        I, R = C.shape[0], C.shape[2]
+        Xk = X.reshape(I, -1, 1) if k == 0 else X.reshape(I, -1, R)
+        X = (Xk[:, :, None, :] * C[:, None, :, :]).sum(dim=0)
+    return X.sum(dim=-1).reshape(b, -1)
