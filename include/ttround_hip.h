@@ -54,7 +54,8 @@ extern "C" {
 /* ABI version of this header: bumped whenever an exported signature changes (round 2 inserted `gparts` / `stride_gpart` into
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
-   symbols fails at load, in the binding and in build()).  ttr_version() returns the value the library was built with; the Python
+   symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
+   ttr_gather_grad_stage_rows.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -769,6 +770,28 @@ int ttr_spd_solve(int dtype, int64_t n_items, int64_t K, const void* Gp, const v
                   const void* counts, void* stream);
 int ttr_pinv_finish(int dtype, int64_t n_items, int64_t K, const void* V, const void* sigma, const void* t, const void* status,
                     void* X, int64_t inner, int64_t s_item, int64_t s_a, int64_t s_b, void* stream);
+
+/*
+ * Gradient of one core from the samples (added under ABI 17; the backward of the differentiable point evaluation t[X], the step
+ * torch autograd takes in the reference's tn.optimize loops: tensor.py:1357-1378 under autograd).  With the left interfaces
+ * L [P, r0] and the right interfaces R [P, r1] of a mode (row-major, leading dimensions ldl >= r0 / ldr >= r1; R seeded with the
+ * incoming gradient),
+ *     dG[:, i, :] = sum over the tasks of slice i, in task order, of  sum_{p in task} L[p]^T R[p]
+ * dG a contiguous [r0, I, r1] tensor.  Tasks as for ttr_als_normal: task t is the run perm[task_begin[t] .. task_end[t]) of the
+ * samples of ONE slice (perm: int64 sample numbers grouped by slice), task_off (int64 [I + 1]) gives the tasks of each slice.
+ * A slice without tasks and an empty task give exact zeros.
+ * One workgroup per (task, 64 x 64 tile of (a, b)); the sample axis is the K dimension of v_mfma_f32_16x16x4_f32 /
+ * v_mfma_f64_16x16x4_f64 (true fp32 / fp64 inputs), the rows gathered through perm into LDS, ttr_gather_grad_stage_rows(dtype, r0,
+ * r1) samples per pass; ranks and runs that are no multiple of the tile are padded with zeros in LDS.  No atomics: a slice with one
+ * task writes dG directly, a slice with several writes partials ([r0, r1] per task) to `workspace`
+ * (ttr_gather_grad_workspace_bytes) and a second launch sums them in task order: the same inputs give the same bits.
+ * Ranks <= 512 (TTR_E_UNSUPPORTED above).  ntasks == 0 writes zeros.  No host synchronisation.
+ */
+int64_t ttr_gather_grad_stage_rows(int dtype, int64_t r0, int64_t r1);
+int64_t ttr_gather_grad_workspace_bytes(int dtype, int64_t ntasks, int64_t r0, int64_t r1);
+int ttr_gather_grad(int dtype, int64_t I, int64_t ntasks, int64_t r0, int64_t r1, const void* L, int64_t ldl, const void* R,
+                    int64_t ldr, const void* perm, const void* task_begin, const void* task_end, const void* task_off, void* dG,
+                    void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * Sparse TT-SVD from samples (ABI 15; interpolation.py:122-218, `sparse_tt_svd`): the TT-SVD of the tensor that holds P samples

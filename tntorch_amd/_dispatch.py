@@ -5,18 +5,22 @@ import torch
 from . import _hostops
 
 
-def ops_for(t: torch.Tensor):
+def ops_for(t: torch.Tensor, grad: bool = False):
     """Return the module implementing the sweeps for tensor ``t``.
 
     A CUDA/HIP tensor ALWAYS maps to the hand-written kernels; if the library is missing
     or the dtype is unsupported this raises -- it never silently computes on the CPU or
     through torch's own GPU linear algebra.
+
+    A device tensor that requires grad is refused, so that no kernel cuts an autograd graph silently -- unless the caller passes
+    ``grad=True``: it then calls only operations that carry a backward pass of their own (autodiff.py: ``mode_mul``,
+    ``decompress``, ``dense_dist``).
     """
     if t.device.type == "cpu":
         return _hostops
     if t.device.type != "cuda":
         raise RuntimeError(f"tntorch_amd: unsupported device {t.device}")
-    if getattr(t, "requires_grad", False):
+    if getattr(t, "requires_grad", False) and not grad:
         raise NotImplementedError("tntorch_amd: the HIP kernels are not differentiable; detach the tensor or use CPU tensors")
     from . import _hip, _hipops
 

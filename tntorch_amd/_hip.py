@@ -1066,6 +1066,44 @@ def als_normal(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: t
     return Gp, hp
 
 
+def gather_grad_stage_rows(dt: torch.dtype, r0: int, r1: int) -> int:
+    """Samples ttr_gather_grad stages per pass for these ranks (a multiple of 4)."""
+    return int(lib().ttr_gather_grad_stage_rows(dtype_code(dt), int(r0), int(r1)))
+
+
+@_on_device
+def gather_grad(L: torch.Tensor, R: torch.Tensor, perm: torch.Tensor, task_begin: torch.Tensor, task_end: torch.Tensor,
+                task_off: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_gather_grad: dG [r0, I, r1], dG[:, i, :] = sum over the tasks of slice i (task_off, int64 [I + 1]) of
+    sum_p L[p]^T R[p] over the samples perm[task_begin[t]:task_end[t]] (L [P, r0], R [P, r1], unit column stride).  ``out``: a
+    contiguous [r0, I, r1] tensor; ``workspace``: uint8, at least ttr_gather_grad_workspace_bytes (allocated when None)."""
+    dt = dtype_code(L.dtype)
+    assert L.dim() == 2 and R.dim() == 2 and L.dtype == R.dtype and L.shape[0] == R.shape[0]
+    if L.shape[1] > 1 and L.stride(1) != 1:
+        L = L.contiguous()
+    if R.shape[1] > 1 and R.stride(1) != 1:
+        R = R.contiguous()
+    r0, r1 = int(L.shape[1]), int(R.shape[1])
+    ldl = int(L.stride(0)) if L.shape[0] > 1 else r0
+    ldr = int(R.stride(0)) if R.shape[0] > 1 else r1
+    T = int(task_begin.shape[0])
+    I = int(task_off.shape[0]) - 1
+    assert task_begin.dtype == task_end.dtype == task_off.dtype == perm.dtype == torch.int64 and task_end.shape[0] == T and I >= 1
+    if L.shape[0] == 0:
+        T = 0  # no samples: every task is empty, and the library writes zeros for ntasks == 0
+    if out is None:
+        out = torch.empty((r0, I, r1), dtype=L.dtype, device=L.device)
+    assert tuple(out.shape) == (r0, I, r1) and out.is_contiguous() and out.dtype == L.dtype
+    wsb = int(lib().ttr_gather_grad_workspace_bytes(dt, T, r0, r1))
+    if wsb < 0:
+        raise ValueError("ttr_gather_grad_workspace_bytes: bad arguments")
+    ws = workspace if workspace is not None else _workspace(wsb, L.device, 1)
+    _call("ttr_gather_grad", dt, I, T, r0, r1, _ptr(L), ldl, _ptr(R), ldr, perm.contiguous().data_ptr(),
+          task_begin.contiguous().data_ptr(), task_end.contiguous().data_ptr(), task_off.contiguous().data_ptr(), out.data_ptr(),
+          ws.data_ptr(), int(ws.numel()))
+    return out
+
+
 def _xout(X: torch.Tensor, inner: int):
     """(item, k) -> X[item, k // inner, k % inner] for a [n_items, K // inner, inner] view X (any strides)."""
     assert X.dim() == 3 and X.shape[2] == inner

@@ -987,12 +987,22 @@ def truncated_svd(M3, delta, eps, rmax, left_ortho, algorithm, batch):
 
 
 # ----------------------------------------------------------------------------------------------
+def _needs_grad(*tensors) -> bool:
+    """Does autograd record an operation on these operands?  The differentiable routes (autodiff.py) are taken then, and only by
+    the callers that ask for them (``ops_for(t, grad=True)``); every other operation refuses such operands before it gets here."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def mode_mul(core4: torch.Tensor, M3: torch.Tensor, trans: bool = False) -> torch.Tensor:
     """[B, r0, S, r1] x_2 [B, a, S] -> [B, r0, a, r1] (the einsum of tensor.py:1790-1798, 1999-2002) as ONE batched GEMM
     over the B * r0 slices ``core[b, r0]`` (S x r1, contiguous where they lie) with the small matrix as the left
     operand: out[b, r0] = M[b] @ core[b, r0].  Neither the core nor the result is permuted (round 2 moved both through
     layout copies); the a x S matrix is the only thing replicated (r0 times, KB).  ``trans``: the matrix is given as [B, S, a]
     and enters the GEMM as a transposed operand (it is not copied)."""
+    if _needs_grad(core4, M3):
+        from . import autodiff
+
+        return autodiff.mode_mul(core4, M3, trans)
     Bt, r0, S, r1 = core4.shape
     a = M3.shape[2] if trans else M3.shape[1]
     core4 = core4 if core4.is_contiguous() else core4.contiguous()
@@ -1672,14 +1682,20 @@ def decompress(c: Sequence[torch.Tensor]) -> torch.Tensor:
     """tensor.py:1639-1687 for TT cores [B, r0, I, r1]: chain of unfolding GEMMs, left to right.
     Returns [B, I_1, ..., I_N] (boundary ranks > 1 are summed away, as the reference does)."""
     Bt = c[0].shape[0]
+    gemm, sum_last = _hip.gemm, _sum_last
+    if _needs_grad(*c):  # Tensor.torch() under autograd: the same chain on the differentiable GEMM
+        from . import autodiff
+
+        gemm = autodiff.gemm
+        sum_last = lambda x3: gemm(x3, torch.ones((x3.shape[0], x3.shape[2], 1), dtype=x3.dtype, device=x3.device))  # noqa: E731
     acc = c[0].reshape(Bt, -1, c[0].shape[-1])
     for core in c[1:]:
-        acc = _hip.gemm(acc, core.reshape(Bt, core.shape[1], -1)).reshape(Bt, -1, core.shape[-1])
+        acc = gemm(acc, core.reshape(Bt, core.shape[1], -1)).reshape(Bt, -1, core.shape[-1])
     r0, rN = c[0].shape[1], c[-1].shape[-1]
     if rN > 1:
-        acc = _sum_last(acc)
+        acc = sum_last(acc)
     if r0 > 1:
-        acc = _sum_last(acc.reshape(Bt, r0, -1).transpose(1, 2).contiguous())
+        acc = sum_last(acc.reshape(Bt, r0, -1).transpose(1, 2).contiguous())
     return acc.reshape([Bt] + [core.shape[2] for core in c])
 
 
@@ -1710,6 +1726,10 @@ def dense_norm(a: torch.Tensor) -> torch.Tensor:
 
 def dense_dist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """||a - b||: the difference through ttr_gemm_axpby (b as an n x 1 times 1 x 1 product), then ttr_norm."""
+    if _needs_grad(a, b):
+        from . import autodiff
+
+        return autodiff.dense_dist(a, b)
     n = a.numel()
     d = a.reshape(1, n, 1).clone()
     one = torch.ones((1, 1, 1), dtype=a.dtype, device=a.device)
@@ -2133,6 +2153,15 @@ def als_core(L: torch.Tensor, R: torch.Tensor, w: Optional[torch.Tensor], y: tor
         _hip.spd_solve(Gp, hp, plan.toff[i0 : i1 + 1], t0, X, r1, Gsum, hsum, status, plan.counts[i0:i1])
         _pinv_fallback(Gsum, hsum, status, X, r1)
     return core
+
+
+# ------------------------------------------------------------------------------------------------ core gradients from samples
+GradPlan = _hostops.GradPlan  # the tasks of one mode (host-built, uploaded once)
+
+
+def gather_grad(L: torch.Tensor, R: torch.Tensor, perm: torch.Tensor, plan: GradPlan) -> torch.Tensor:
+    """dG [r0, I, r1] = per-slice sum of L[p]^T R[p] over the samples of ``perm`` as ``plan`` groups them (ttr_gather_grad)."""
+    return _hip.gather_grad(L, R, perm, plan.tb, plan.te, plan.toff)
 
 
 # ------------------------------------------------------------------------------------------------ sparse TT-SVD (interpolation.py)

@@ -354,6 +354,48 @@ def dense_dist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.dist(a, b)
 
 
+# ---------------------------------------------------------------------------------------------- core gradients from samples
+GRAD_TASK_SAMPLES = 4096  # samples per ttr_gather_grad task: longer slices are split, so skewed data does not sit on one workgroup
+
+
+class GradPlan:
+    """The tasks of one mode for ``ttr_gather_grad``: slice i with n samples becomes ceil(n / task_samples) tasks of nearly equal
+    length (AlsPlan's splitting rule), a slice without samples gets none.  Built on the host from the per-slice counts and
+    uploaded once."""
+
+    def __init__(self, counts: Sequence[int], device, task_samples: Optional[int] = None):
+        ts = int(GRAD_TASK_SAMPLES if task_samples is None else task_samples)
+        if ts < 1:
+            raise ValueError("GradPlan: task_samples must be at least 1")
+        tb, te, toff, pos = [], [], [0], 0
+        for n in counts:
+            n = int(n)
+            nt = -(-n // ts)
+            for k in range(nt):
+                tb.append(pos + (n * k) // nt)
+                te.append(pos + (n * (k + 1)) // nt)
+            pos += n
+            toff.append(len(tb))
+        self.ntasks, self.nslices, self.nsamples = len(tb), len(toff) - 1, pos
+        self.tb = torch.tensor(tb, dtype=torch.int64, device=device)
+        self.te = torch.tensor(te, dtype=torch.int64, device=device)
+        self.toff = torch.tensor(toff, dtype=torch.int64, device=device)
+
+
+def gather_grad(L: torch.Tensor, R: torch.Tensor, perm: torch.Tensor, plan: GradPlan) -> torch.Tensor:
+    """Mirror of ttr_gather_grad: dG [r0, I, r1], dG[:, i, :] = sum of L[p]^T R[p] over the samples of slice i, i.e. over the runs
+    perm[tb[t]:te[t]] of the slice's tasks (``index_add_`` of the outer products; any float dtype)."""
+    r0, r1, I = L.shape[1], R.shape[1], plan.nslices
+    owner = torch.repeat_interleave(torch.arange(I, device=L.device), plan.toff[1:] - plan.toff[:-1])  # slice of each task
+    lens = plan.te - plan.tb
+    pos = torch.repeat_interleave(plan.tb, lens) + (torch.arange(int(lens.sum()), device=L.device)
+                                                   - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens))
+    q = perm[pos]
+    dG = torch.zeros((I, r0, r1), dtype=L.dtype, device=L.device)
+    dG.index_add_(0, torch.repeat_interleave(owner, lens), L[q, :, None] * R[q, None, :])
+    return dG.permute(1, 0, 2).contiguous()
+
+
 # ---------------------------------------------------------------------------------------------- derivatives (derivatives.py:72-302)
 def _diff_pass(X: torch.Tensor, periodic: bool, inv_step: float) -> torch.Tensor:
     """One pass of derivatives.py:96-129 on X [R, I, C]: interior rows x[i+1] - x[i-1], rows 0 and I-1 twice the one-sided

@@ -1,0 +1,349 @@
+"""Gradient-based fitting: ``tn.optimize``, ``tn.dof`` (autodiff.py:10-121) and the differentiable operations of the device path.
+
+The reference leaves differentiation to torch autograd over its einsum chains.  The HIP kernels are opaque to autograd, so the
+operations that the fitting losses of the reference's tutorials are made of carry hand-written backward passes here, each one
+``torch.autograd.Function`` over detached operands:
+
+- ``t[X]`` with index arrays on the first k modes (``point_eval``): forward one ``ttr_gather_step`` per mode,
+  the left interfaces kept; backward one ``ttr_gather_grad`` per core that needs a gradient (the per-slice sum of outer
+  products L[p]^T R[p] on the matrix cores) and one ``ttr_gather_step`` per mode that moves the right interface;
+- ``mode_mul`` (Tucker factors), ``gemm`` (the chain of ``Tensor.torch()``) and ``dense_dist`` (``tn.dist`` /
+  ``tn.relative_error`` against a dense tensor): existing kernels in both directions.
+
+Everything else keeps refusing device operands that require grad (``Tensor._norm4`` / ``_dispatch.ops_for``), as do batched
+trains, CP cores and keys of any other form.  CPU trains need none of this: the host mirror is plain torch.  No double backward.
+"""
+
+from __future__ import annotations
+
+import time
+from collections import OrderedDict
+from typing import List, Optional, Sequence
+
+import torch
+from torch.autograd.function import once_differentiable
+
+__all__ = ["optimize", "dof"]
+
+_OOB = "index out of range: an index array entry lies outside its mode"
+
+
+# ---------------------------------------------------------------------------------------------- grouping plans of index columns
+PLAN_BUILDS = 0         # plans built so far (tests: an optimize loop sorts and reads counts back once, not once per iteration)
+PLAN_CACHE_SIZE = 16    # least recently used entries beyond this are dropped
+TASK_SAMPLES: Optional[int] = None  # samples per ttr_gather_grad task (None: _hostops.GRAD_TASK_SAMPLES); tests split small slices
+_plans: "OrderedDict[int, tuple]" = OrderedDict()
+_plan_serial = 0
+
+
+def _plan_key(col: torch.Tensor, I: int):
+    return (col.storage_offset(), tuple(col.stride()), tuple(col.shape), col.dtype, col._version, int(I), TASK_SAMPLES)
+
+
+def build_plan(col: torch.Tensor, I: int):
+    """(perm, GradPlan) of one validated index column: indices wrapped, sample numbers sorted by slice (stable), per-slice counts
+    read back once."""
+    global PLAN_BUILDS
+    from . import _hostops
+
+    PLAN_BUILDS += 1
+    v = torch.remainder(col, I)
+    perm = torch.sort(v, stable=True).indices
+    counts = torch.bincount(v, minlength=I).cpu().tolist() if col.shape[0] else [0] * I
+    return perm, _hostops.GradPlan(counts, col.device, TASK_SAMPLES)
+
+
+def plan_for(col: torch.Tensor, I: int, cache: bool = True):
+    """The plan of ``col``, reused while the same unmodified tensor is passed again: an entry holds the base tensor object itself
+    (so its identity cannot be recycled) and matches on that object, the view's offset, strides and length, and the version
+    counter that every in-place write bumps.  Never on a bare data pointer."""
+    global _plan_serial
+    if not cache:
+        return build_plan(col, I)
+    base = col._base if col._base is not None else col
+    key = _plan_key(col, I)
+    for serial, (b, k, value) in _plans.items():
+        if b is base and k == key:
+            _plans.move_to_end(serial)
+            return value
+    value = build_plan(col, I)
+    _plan_serial += 1
+    _plans[_plan_serial] = (base, key, value)
+    while len(_plans) > PLAN_CACHE_SIZE:
+        _plans.popitem(last=False)
+    return value
+
+
+def clear_plans() -> None:
+    _plans.clear()
+
+
+# ---------------------------------------------------------------------------------------------- t[X]
+class _PointEval(torch.autograd.Function):
+    """out [1, P, r_k] = prod_n cores[n][:, cols[n][p], :] for cores [r_n, I_n, r_{n+1}] with r_0 = 1."""
+
+    @staticmethod
+    def forward(ctx, cols, cacheable, *cores):
+        from . import _hip
+
+        dev, dt = cores[0].device, cores[0].dtype
+        k, P = len(cores), cols[0].shape[0]
+        flags = torch.zeros(k, dtype=torch.int32, device=dev)
+        Ls = [torch.ones((P, 1), dtype=dt, device=dev)]
+        for n in range(k):
+            if P == 0:  # nothing to evaluate (and an empty tensor has no address to pass)
+                Ls.append(torch.empty((0, cores[n].shape[2]), dtype=dt, device=dev))
+            else:
+                Ls.append(_hip.gather_step(Ls[-1], None, cores[n], cols[n], flag=flags[n:n + 1]))
+        if P and int(flags.max().item()):  # the one host read of the call
+            raise IndexError(_OOB)
+        needs = [bool(x) for x in ctx.needs_input_grad[2:]]
+        ctx.plans = [plan_for(cols[n], cores[n].shape[1], cacheable[n]) if needs[n] else None for n in range(k)]
+        ctx.cols = cols
+        ctx.save_for_backward(*cores, *Ls[:k])
+        return Ls[k].reshape(1, P, cores[-1].shape[2])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import _hip, _hipops
+
+        k = len(ctx.cols)
+        cores, Ls = ctx.saved_tensors[:k], ctx.saved_tensors[k:]
+        needs = [bool(x) for x in ctx.needs_input_grad[2:]]
+        if g.shape[1] == 0:  # no points: zero gradients
+            return (None, None) + tuple(torch.zeros_like(c) if need else None for c, need in zip(cores, needs))
+        R = g.reshape(g.shape[1], g.shape[2]).contiguous()
+        grads: List[Optional[torch.Tensor]] = [None] * k
+        for n in range(k - 1, -1, -1):
+            if needs[n]:
+                perm, plan = ctx.plans[n]
+                grads[n] = _hipops.gather_grad(Ls[n], R, perm, plan)
+            if any(needs[:n]):  # R_{n-1}[p] = R_n[p] G_n[:, i_p, :]^T: the step on the core with its rank strides swapped
+                R = _hip.gather_step(R, None, cores[n].permute(2, 1, 0), ctx.cols[n])
+        return (None, None) + tuple(grads)
+
+
+def point_eval(cores3: Sequence[torch.Tensor], cols: Sequence[torch.Tensor], cacheable: Optional[Sequence[bool]] = None) -> torch.Tensor:
+    """Differentiable ``[1, P, r_k]`` core of the index-array block over device cores [r_n, I_n, r_{n+1}] (r_0 = 1)."""
+    if cacheable is None:
+        cacheable = [True] * len(cols)
+    return _PointEval.apply(list(cols), list(cacheable), *cores3)
+
+
+def wants_grad(t) -> bool:
+    """Does ``t[key]`` have to be recorded by autograd on the device path?"""
+    if not torch.is_grad_enabled():
+        return False
+    return any(x is not None and x.is_cuda and x.requires_grad for x in list(t.cores) + list(t.Us))
+
+
+def getitem(t, key: list):
+    """``t[key]`` for a processed key (one entry per mode) on a device train with parameters that require grad: index arrays on
+    the first k >= 1 modes, slices on the rest."""
+    from . import _hipops
+    from .indexing import _index_column, _kind
+    from .tensor import Tensor
+
+    def refuse(what):
+        raise NotImplementedError("tntorch_amd: {} is not differentiable on the device (supported: index arrays on the first "
+                                  "modes of a non-batch TT / TT-Tucker train, slices on the rest); detach the cores or use CPU "
+                                  "tensors".format(what))
+
+    if t.batch:
+        refuse("indexing a batched train")
+    if any(c.dim() != 3 for c in t.cores):
+        refuse("indexing CP cores")
+    kinds = [_kind(x) for x in key]
+    k = 0
+    while k < len(kinds) and kinds[k] == "index":
+        k += 1
+    if k == 0 or any(kind != "slice" for kind in kinds[k:]):
+        refuse("this key")
+    if t.cores[0].shape[0] != 1:
+        refuse("a leading boundary rank above 1")
+    dev = t.cores[0].device
+    _hipops._hip.lib()
+    _hipops._hip.dtype_code(t.cores[0].dtype)
+    cols = [_index_column(x, dev) for x in key[:k]]
+    if any(len(c) != len(cols[0]) for c in cols):
+        raise ValueError("Index arrays must have the same length")
+    cacheable = [isinstance(x, torch.Tensor) and x.device == dev and x.dtype in (torch.int32, torch.int64) for x in key[:k]]
+    block = []
+    for n in range(k):
+        c = t.cores[n]
+        block.append(c if t.Us[n] is None else mode_mul(c[None], t.Us[n][None])[0])
+    cores, Us = [point_eval(block, cols, cacheable)], [None]
+    for n in range(k, len(t.cores)):
+        if t.Us[n] is None:
+            cores.append(t.cores[n][:, key[n], :])
+            Us.append(None)
+        else:
+            cores.append(t.cores[n])
+            Us.append(t.Us[n][key[n], :])
+    return Tensor(cores, Us=Us)
+
+
+# ---------------------------------------------------------------------------------------------- existing kernels, both directions
+class _Gemm(torch.autograd.Function):
+    """C[b] = A[b] @ B[b] (ttr_gemm); dA = g B^T, dB = A^T g."""
+
+    @staticmethod
+    def forward(ctx, A, B):
+        from . import _hip
+
+        ctx.save_for_backward(A, B)
+        return _hip.gemm(A, B)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import _hip
+
+        A, B = ctx.saved_tensors
+        dA = _hip.gemm(g, B, transB=True) if ctx.needs_input_grad[0] else None
+        dB = _hip.gemm(A, g, transA=True) if ctx.needs_input_grad[1] else None
+        return dA, dB
+
+
+def gemm(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    return _Gemm.apply(A, B)
+
+
+class _ModeMul(torch.autograd.Function):
+    """[B, r0, S, r1] x_2 [B, a, S] -> [B, r0, a, r1]; the core's gradient is mode_mul(trans=True), the factor's one GEMM."""
+
+    @staticmethod
+    def forward(ctx, core4, M3):
+        from . import _hipops
+
+        ctx.save_for_backward(core4, M3)
+        return _hipops.mode_mul(core4, M3)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import _hip, _hipops
+
+        core4, M3 = ctx.saved_tensors
+        Bt, r0, S, r1 = core4.shape
+        a = M3.shape[1]
+        dcore = _hipops.mode_mul(g, M3, trans=True) if ctx.needs_input_grad[0] else None
+        dM = None
+        if ctx.needs_input_grad[1]:  # dM[b] = sum_{r0} g[b, r0] core[b, r0]^T
+            gp = g.permute(0, 2, 1, 3).reshape(Bt, a, r0 * r1)
+            cp = core4.permute(0, 2, 1, 3).reshape(Bt, S, r0 * r1)
+            dM = _hip.gemm(gp, cp, transB=True)
+        return dcore, dM
+
+
+def mode_mul(core4: torch.Tensor, M3: torch.Tensor, trans: bool = False) -> torch.Tensor:
+    if trans:
+        raise NotImplementedError("tntorch_amd: mode_mul with a transposed factor is not differentiable on the device")
+    return _ModeMul.apply(core4, M3)
+
+
+class _DenseDist(torch.autograd.Function):
+    """||a - b|| (ttr_gemm_axpby, ttr_norm); the gradients are +-(a - b) g / dist, zero where dist == 0."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        from . import _hip
+
+        n = a.numel()
+        d = a.reshape(1, n, 1).clone()
+        one = torch.ones((1, 1, 1), dtype=a.dtype, device=a.device)
+        _hip.gemm_axpby(b.reshape(1, n, 1), one, d, -1.0, 1.0)
+        dist = _hip.norm(d.reshape(1, -1))[0]
+        ctx.save_for_backward(d, dist)
+        ctx.shapes = (a.shape, b.shape)
+        return dist
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import _hip
+
+        d, dist = ctx.saved_tensors
+        s = torch.where(dist > 0, g / dist, torch.zeros_like(dist)).reshape(1, 1, 1)  # one element
+        ga = _hip.gemm(d, s).reshape(ctx.shapes[0]) if ctx.needs_input_grad[0] else None
+        gb = _hip.gemm(d, -s).reshape(ctx.shapes[1]) if ctx.needs_input_grad[1] else None
+        return ga, gb
+
+
+def dense_dist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    if a.numel() != b.numel():
+        raise ValueError("dist: the operands have {} and {} elements".format(a.numel(), b.numel()))
+    return _DenseDist.apply(a, b)
+
+
+# ---------------------------------------------------------------------------------------------- autodiff.py:10-121
+def _parameters(tensors) -> list:
+    from .tensor import Tensor
+
+    params = []
+    for t in tensors:
+        if isinstance(t, Tensor):
+            if t.batch:
+                raise ValueError("Batched tensors are not supproted.")
+            params += [c for c in t.cores if c.requires_grad]
+            params += [U for U in t.Us if U is not None and U.requires_grad]
+        elif t.requires_grad:
+            params.append(t)
+    return params
+
+
+def optimize(tensors, loss_function, optimizer=torch.optim.Adam, tol=1e-4, max_iter=1e4, print_freq=500, verbose=True):
+    """Iterative fitting (autodiff.py:10-101): ``tensors`` (one or several ``Tensor`` / ``torch.Tensor``) are passed to
+    ``loss_function``, which returns a scalar or a tuple of scalars, and their cores and factors with ``requires_grad=True`` are
+    updated in place by ``optimizer`` (a callable on the parameter list; default ``torch.optim.Adam``).
+
+    It stops when the loss falls to ``tol`` or its relative improvement does (and the improvement is slowing down), or after
+    ``max_iter`` iterations; progress is printed every ``print_freq`` iterations.  CPU and device trains; the total loss is read
+    from the device once per iteration.  Batched tensors and a call without parameters raise ValueError."""
+    if not isinstance(tensors, (list, tuple)):
+        tensors = [tensors]
+    params = _parameters(tensors)
+    if not params:
+        raise ValueError("There are no parameters to optimize. Did you forget a requires_grad=True somewhere?")
+    opt = optimizer(params)
+    width = len("{}".format(max_iter))
+
+    def report(it, parts, total, end="\n"):
+        line = "iter: {: <{}} | loss: ".format(it, width) + " + ".join("{:10.6f}".format(p.item()) for p in parts)
+        if len(parts) > 1:
+            line += " = {:10.4}".format(total)
+        print(line + " | total time: {:9.4f}".format(time.time() - start), end=end)
+
+    history: List[float] = []
+    start = time.time()
+    it, converged = 0, False
+    while True:
+        opt.zero_grad()
+        parts = loss_function(*tensors)
+        if not isinstance(parts, (tuple, list)):
+            parts = [parts]
+        total = sum(parts)
+        total.backward(retain_graph=True)
+        opt.step()
+        history.append(float(total.detach()))  # the one read of the iteration
+        if it >= 2 and tol is not None:
+            cur, prev, before = history[-1], history[-2], history[-3]
+            small = cur <= tol or (cur != 0 and (prev - cur) / cur <= tol)
+            if small and prev - cur < before - prev:
+                converged = True
+                break
+        if it == max_iter:
+            break
+        if verbose and it % print_freq == 0:
+            report(it, parts, history[-1])
+        it += 1
+    if verbose:
+        report(it, parts, history[-1], end="")
+        print(" <- converged (tol={})".format(tol) if converged else " <- max_iter was reached: {}".format(max_iter))
+
+
+def dof(t) -> int:
+    """Degrees of freedom (autodiff.py:104-121): the number of elements of the cores and factors with ``requires_grad=True``."""
+    nodes = list(t.cores) + [U for U in t.Us if U is not None]
+    return sum(x.numel() for x in nodes if x.requires_grad)

@@ -14,6 +14,9 @@ columns, tensor.py:1086-1093), then walked mode by mode in the cores' ``[B, r, I
 Ints and index arrays on a Tucker mode contract the factor into the core first.  The batch dimension of a batch train is
 selected up front.  CPU cores run torch ops (the host mirror); device cores only go through ``ttr_gemm`` and
 ``ttr_gather_chain`` plus data movement (slicing, ``reshape``), and device index tensors are validated on the device.
+
+Device cores or factors that require grad (with grad mode on) take ``autodiff.getitem`` instead: index arrays on the first modes
+and slices on the rest are differentiable there, every other key raises ``NotImplementedError``.
 """
 
 from __future__ import annotations
@@ -97,6 +100,10 @@ def getitem(t, key: Any):
         key = [key[:, col] for col in range(key.shape[1])]  # tensor.py:1086-1093
     key = _process_key(len(t.shape), key)
 
+    from . import autodiff
+
+    if autodiff.wants_grad(t):  # device parameters that require grad: the differentiable route, or a refusal
+        return autodiff.getitem(t, key)
     c4, Us = t._norm4(), t._norm_us()
     device = c4[0].device
     ops = ops_for(c4[0])

@@ -24,6 +24,7 @@ def dot(t1, t2):
     """Full inner product <t1, t2> (metrics.py:28-116 with k = N, no Tucker factors)."""
     if not isinstance(t1, Tensor) or not isinstance(t2, Tensor):
         a, b = _dense(t1), _dense(t2)
+        ops_for(b)  # (refuses a device operand that requires grad: dense_dot has no backward)
         return ops_for(a).dense_dot(a, b)
     if t1.batch or t2.batch:
         raise ValueError("Batched tensors are not supproted.")
@@ -37,7 +38,7 @@ def dist(t1, t2):
     """Euclidean distance (metrics.py:119-132)."""
     if not isinstance(t1, Tensor) or not isinstance(t2, Tensor):
         a, b = _dense(t1), _dense(t2)
-        return ops_for(a).dense_dist(a, b)
+        return ops_for(a, grad=True).dense_dist(a, b)  # differentiable in both operands on the device (autodiff.dense_dist)
     return torch.sqrt((dot(t1, t1) + dot(t2, t2) - 2 * dot(t1, t2)).clamp(0))
 
 
@@ -49,8 +50,8 @@ def relative_error(gt, approx):
     """
     if not isinstance(gt, Tensor) or not isinstance(approx, Tensor):
         a, b = _dense(gt), _dense(approx)
-        ops = ops_for(a)
-        return ops.dense_dist(a, b) / ops.dense_norm(a)
+        ops = ops_for(a)  # (gt itself may not require grad on the device: dense_norm has no backward)
+        return ops.dense_dist(a, b) / ops.dense_norm(a)  # differentiable in ``approx`` (autodiff.dense_dist)
     dotgt = dot(gt, gt)
     return torch.sqrt((dotgt + dot(approx, approx) - 2 * dot(gt, approx)).clamp(0)) / torch.sqrt(dotgt.clamp(0))
 

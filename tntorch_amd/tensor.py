@@ -215,10 +215,11 @@ class Tensor(object):
             self.round_tucker((1 + eps) / (1 + reached) - 1, algorithm=algorithm)
 
     # ------------------------------------------------------------------ layout helpers
-    def _norm4(self) -> List[torch.Tensor]:
+    def _norm4(self, grad: bool = False) -> List[torch.Tensor]:
         """Cores as [B, r0, I, r1] views (B = 1 for non-batch tensors); CP factors [I, R] become TT cores whose
-        slices are diagonal (tensor.py:1717-1769: first [1, I, R], last [R, I, 1], middle [R, I, R])."""
-        if any(c.is_cuda and c.requires_grad for c in self.cores):
+        slices are diagonal (tensor.py:1717-1769: first [1, I, R], last [R, I, 1], middle [R, I, R]).  ``grad``: the caller
+        differentiates what it does with them (autodiff.py); everyone else is refused device parameters that require grad."""
+        if not grad and any(x is not None and x.is_cuda and x.requires_grad for x in list(self.cores) + list(self.Us)):
             raise NotImplementedError(
                 "tntorch_amd: the HIP kernels are not differentiable (autograd would silently see constants); "
                 "detach the cores or run the rounding on CPU tensors")
@@ -253,12 +254,12 @@ class Tensor(object):
     def _has_factors(self) -> bool:
         return any(U is not None for U in self.Us)
 
-    def _absorbed4(self) -> List[torch.Tensor]:
-        """Cores [B, r0, I, r1] with the Tucker factors contracted in."""
-        c = self._norm4()
+    def _absorbed4(self, grad: bool = False) -> List[torch.Tensor]:
+        """Cores [B, r0, I, r1] with the Tucker factors contracted in (``grad``: as for ``_norm4``; ``mode_mul`` is differentiable)."""
+        c = self._norm4(grad)
         if not self._has_factors():
             return c
-        return ops_for(c[0]).absorb_factors(c, self._norm_us())
+        return ops_for(c[0], grad).absorb_factors(c, self._norm_us())
 
     # ------------------------------------------------------------------ properties (tensor.py:836-919)
     @property
@@ -337,8 +338,9 @@ class Tensor(object):
 
     def torch(self):
         """Decompress into a dense torch tensor (tensor.py:1639-1687, TT / TT-Tucker)."""
-        c = self._absorbed4()
-        out = ops_for(c[0]).decompress(c)  # device tensors: chain of MFMA GEMMs (ttr_gemm)
+        grad = (not self.batch) and all(x.dim() == 3 for x in self.cores)  # differentiable on the device: non-batch TT / TT-Tucker
+        c = self._absorbed4(grad)
+        out = ops_for(c[0], grad).decompress(c)  # device tensors: chain of MFMA GEMMs (ttr_gemm)
         return out if self.batch else out[0]
 
     def numpy(self):
