@@ -55,7 +55,8 @@ extern "C" {
    ttr_eigh_trunc = 2; round 3 additions = 3 ... 7, the last one ttr_eigh_top; round 4: 8 = rows32 / skip_zero_rows, 9 = ttr_carry_rows32;
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
-   ttr_gather_grad_stage_rows.  ttr_version() returns the value the library was built with; the Python
+   ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
+   ttr_ttm_grad_core.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1159,6 +1160,38 @@ int ttr_ttm_step(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t 
                  const void* G, const int64_t* g_strides, void* Y, void* stream);
 int ttr_cpm_step(int dtype, int64_t I, int64_t D, int64_t O, int64_t R, int x_has_rank, const void* X, const void* C, void* Y,
                  void* stream);
+
+/*
+ * The backward of ttr_ttm_step (added under ABI 17; what torch autograd derives from the einsum chain of matrix.py:420-443
+ * `tt_multiply`).  X [I, D, R], G [R, I, O, S], dY [D, O, S], dX [I, D, R] and dG [R, I, O, S] are all
+ * contiguous (there are no stride arguments).  dX of step k, as it lies, is dY of step k - 1: the backward chain copies nothing.
+ *
+ * ttr_ttm_grad_input   dX[i, dd, r] = sum_{o, s} dY[dd, o, s] G[r, i, o, s].  A GEMM with M = D, N = I R and K = O S, K contiguous
+ *                      in both operands and never split across workgroups; the 64 x 64 output tile is staged in LDS and stored
+ *                      in runs of equal i (the mirror of ttr_ttm_step's two-stride load), in 16-byte packs where R is a multiple
+ *                      of 16 bytes of elements and dX is 16-byte aligned.
+ * ttr_ttm_grad_core    dG[r, i, o, s] = sum_dd X[i, dd, r] dY[dd, o, s].  M = I R (two-stride load), N = O S, K = D, cut into
+ *                      slabs of ttr_ttm_grad_core_slab_rows rows; a workgroup owns one (64 x 64 tile, slab) pair.  The slab rule
+ *                      reads the six arguments only, never the device: with tiles = ceil(I R / 64) ceil(O S / 64) and
+ *                      want = max(1, 1024 / tiles), slab_rows = max(256, ceil(D / want) rounded up to a multiple of 32).  One
+ *                      slab (D <= slab_rows): dG is written directly, `workspace` may be null.  Several: the partial tiles go to
+ *                      `workspace` [nslab, I R, O S] (ttr_ttm_grad_core_workspace_bytes; 0 for one slab) and a second launch sums
+ *                      them in slab order: eight runs of ceil(nslab / 8) consecutive slabs, each summed in increasing slab
+ *                      order, the run sums then added in run order (an association fixed by nslab alone).  A missing or short
+ *                      workspace is TTR_E_WORKSPACE.
+ * Both run on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 with operands and accumulators in the dtype and 64-bit element
+ * offsets; column tiles of 16 past N and quads of k past K are not multiplied.  No atomics, no host synchronisation: the same
+ * call gives the same bits, wherever the buffers lie.  Before any launch, with the output untouched: TTR_E_INVALID for a bad
+ * dtype, an extent below 1, a null pointer or an output that is one of the inputs; TTR_E_UNSUPPORTED for D, I R or O S above
+ * 2^31 - 1 and for an operand of 2^57 elements or more (the two queries return the same codes, < 0).  Profiling kind:
+ * TTR_PROF_GEMM.
+ */
+int ttr_ttm_grad_input(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S, const void* dY, const void* G, void* dX,
+                       void* stream);
+int64_t ttr_ttm_grad_core_slab_rows(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S);
+int64_t ttr_ttm_grad_core_workspace_bytes(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S);
+int ttr_ttm_grad_core(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S, const void* X, const void* dY, void* dG,
+                      void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,8 +17,8 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``,
 and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``, and the matrix formats of
 ``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``, and gradient-based fitting (``autodiff.py``):
-``tn.optimize`` and ``tn.dof``, with ``t[X]`` at index arrays, ``Tensor.torch()`` and ``tn.dist`` / ``tn.relative_error`` against a
-dense tensor differentiable on the device (hand-written backward passes; every other operation refuses device cores that require
+``tn.optimize`` and ``tn.dof``, with ``t[X]`` at index arrays, ``Tensor.torch()``, ``tn.dist`` / ``tn.relative_error`` against a
+dense tensor and ``tn.tt_multiply`` (in the cores and the tensor) differentiable on the device (hand-written backward passes; every other operation refuses device cores that require
 grad).
 """
 

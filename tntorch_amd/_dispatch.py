@@ -14,7 +14,7 @@ def ops_for(t: torch.Tensor, grad: bool = False):
 
     A device tensor that requires grad is refused, so that no kernel cuts an autograd graph silently -- unless the caller passes
     ``grad=True``: it then calls only operations that carry a backward pass of their own (autodiff.py: ``mode_mul``,
-    ``decompress``, ``dense_dist``).
+    ``decompress``, ``dense_dist``, ``tt_matvec``).
     """
     if t.device.type == "cpu":
         return _hostops

@@ -1652,3 +1652,60 @@ def cpm_step(X: torch.Tensor, C: torch.Tensor, out: Optional[torch.Tensor] = Non
     assert out.numel() == D * O * R and out.is_contiguous() and out.dtype == X.dtype and out.device == X.device
     _call("ttr_cpm_step", dt, I, D, O, R, int(X.dim() == 3), X.data_ptr(), C.data_ptr(), out.data_ptr())
     return out
+
+
+@_on_device
+def ttm_grad_input(dY: torch.Tensor, G: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ttm_grad_input: dY (D O S elements, read as [D, O, S]), G [R, I, O, S] (a TTMatrix core) -> dX [I, D, R],
+    dX[i, dd, r] = sum_{o, s} dY[dd, o, s] G[r, i, o, s]: the gradient of ttm_step's X.  The entry takes contiguous operands only
+    (it has no stride arguments), so anything else is refused here (ValueError).  ``out``: a contiguous tensor of I D R elements
+    (its shape is not looked at: the caller reads it as the previous step's dY); a fresh [I, D, R] tensor when None."""
+    dt = dtype_code(G.dtype)
+    assert G.dim() == 4 and dY.dtype == G.dtype and dY.device == G.device
+    R, I, O, S = G.shape
+    assert dY.numel() % (O * S) == 0
+    D = dY.numel() // (O * S)
+    if not (dY.is_contiguous() and G.is_contiguous()):
+        raise ValueError("ttm_grad_input: dY and G must be contiguous")
+    if out is None:
+        out = torch.empty((I, D, R), dtype=G.dtype, device=G.device)
+    assert out.numel() == I * D * R and out.is_contiguous() and out.dtype == G.dtype and out.device == G.device
+    _call("ttr_ttm_grad_input", dt, I, D, R, O, S, dY.data_ptr(), G.data_ptr(), out.data_ptr())
+    return out
+
+
+def ttm_grad_core_slab_rows(dt: torch.dtype, I: int, D: int, R: int, O: int, S: int) -> int:
+    """Rows of D one workgroup of ttr_ttm_grad_core sums (a function of these six arguments only)."""
+    return int(lib().ttr_ttm_grad_core_slab_rows(dtype_code(dt), int(I), int(D), int(R), int(O), int(S)))
+
+
+def ttm_grad_core_workspace_bytes(dt: torch.dtype, I: int, D: int, R: int, O: int, S: int) -> int:
+    """Bytes of workspace ttr_ttm_grad_core needs for these sizes (0 where D is one slab)."""
+    return int(lib().ttr_ttm_grad_core_workspace_bytes(dtype_code(dt), int(I), int(D), int(R), int(O), int(S)))
+
+
+@_on_device
+def ttm_grad_core(X: torch.Tensor, dY: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ttm_grad_core: X [I, D, R], dY (D N elements, read as [D, N]; N = O S is taken from ``out``, or is dY.shape[1:] when
+    ``out`` is None and dY is [D, O, S]) -> dG [R, I, O, S], dG[r, i, o, s] = sum_dd X[i, dd, r] dY[dd, o, s]: the gradient of
+    ttm_step's G.  Contiguous operands only (ValueError otherwise).  ``out``: a contiguous [R, I, O, S] tensor; ``workspace``:
+    uint8, at least ttr_ttm_grad_core_workspace_bytes (allocated when None and needed)."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and dY.dtype == X.dtype and dY.device == X.device
+    I, D, R = X.shape
+    if out is None:
+        assert dY.dim() == 3 and dY.shape[0] == D
+        out = torch.empty((R, I, dY.shape[1], dY.shape[2]), dtype=X.dtype, device=X.device)
+    assert out.dim() == 4 and out.shape[0] == R and out.shape[1] == I and out.is_contiguous() and out.dtype == X.dtype and out.device == X.device
+    O, S = out.shape[2], out.shape[3]
+    assert dY.numel() == D * O * S
+    if not (X.is_contiguous() and dY.is_contiguous()):
+        raise ValueError("ttm_grad_core: X and dY must be contiguous")
+    wsb = int(lib().ttr_ttm_grad_core_workspace_bytes(dt, I, D, R, O, S))
+    if wsb < 0:
+        _check(wsb, "ttr_ttm_grad_core_workspace_bytes")
+    ws = workspace if workspace is not None else _workspace(wsb, X.device)
+    _call("ttr_ttm_grad_core", dt, I, D, R, O, S, X.data_ptr(), dY.data_ptr(), out.data_ptr(), _ptr(ws),
+          int(ws.numel()) if ws is not None else 0)
+    return out

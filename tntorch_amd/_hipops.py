@@ -2267,6 +2267,21 @@ def tt_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.T
     return X.view(b, -1)
 
 
+def ttm_step(X: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """One step of the chain above (ttr_ttm_step): X [I, D, R], G [R, I, O, S] -> Y [D, O, S]."""
+    return _hip.ttm_step(X, G.contiguous())
+
+
+def ttm_grad_input(dY: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """The step's gradient with respect to X (ttr_ttm_grad_input): dY [D, O, S], G [R, I, O, S] -> dX [I, D, R]."""
+    return _hip.ttm_grad_input(dY, G.contiguous())
+
+
+def ttm_grad_core(X: torch.Tensor, dY: torch.Tensor) -> torch.Tensor:
+    """The step's gradient with respect to G (ttr_ttm_grad_core): X [I, D, R], dY [D, O, S] -> dG [R, I, O, S]."""
+    return _hip.ttm_grad_core(X, dY)
+
+
 def cp_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.Tensor:
     """x2d [b, prod I_k] times the CP-matrix with the cores C_k [I_k, O_k, R] -> [b, prod O_k]: one ttr_cpm_step per core, then
     the sum over the rank by ttr_mode_reduce."""

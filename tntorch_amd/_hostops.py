@@ -949,6 +949,21 @@ def tt_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.T
     return X.reshape(b, -1)
 
 
+def ttm_step(X: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """Y[dd, o, s] = sum_{i, r} X[i, dd, r] G[r, i, o, s] (ttr_ttm_step): X [I, D, R], G [R, I, O, S] -> Y [D, O, S]."""
+    return torch.einsum("idr,rios->dos", X, G).contiguous()
+
+
+def ttm_grad_input(dY: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """dX[i, dd, r] = sum_{o, s} dY[dd, o, s] G[r, i, o, s] (ttr_ttm_grad_input): dY [D, O, S], G [R, I, O, S] -> dX [I, D, R]."""
+    return torch.einsum("dos,rios->idr", dY, G).contiguous()
+
+
+def ttm_grad_core(X: torch.Tensor, dY: torch.Tensor) -> torch.Tensor:
+    """dG[r, i, o, s] = sum_dd X[i, dd, r] dY[dd, o, s] (ttr_ttm_grad_core): X [I, D, R], dY [D, O, S] -> dG [R, I, O, S]."""
+    return torch.einsum("idr,dos->rios", X, dY).contiguous()
+
+
 def cp_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.Tensor:
     """x2d [b, prod I_k] times the CP-matrix with the cores C_k [I_k, O_k, R] -> [b, prod O_k]: the chain of ttr_cpm_step in
     torch ops (the rank index is carried, step 0 broadcasts X_0 over it), then the sum over the rank."""

@@ -2,11 +2,15 @@
 
 The reference leaves differentiation to torch autograd over its einsum chains.  The HIP kernels are opaque to autograd, so the
 operations that the fitting losses of the reference's tutorials are made of carry hand-written backward passes here, each one
-``torch.autograd.Function`` over detached operands:
+``torch.autograd.Function`` (grad mode is off inside its ``forward``, so the kernels' work is not recorded; the operands are
+passed as they are, not detached copies):
 
 - ``t[X]`` with index arrays on the first k modes (``point_eval``): forward one ``ttr_gather_step`` per mode,
   the left interfaces kept; backward one ``ttr_gather_grad`` per core that needs a gradient (the per-slice sum of outer
   products L[p]^T R[p] on the matrix cores) and one ``ttr_gather_step`` per mode that moves the right interface;
+- ``tt_multiply`` (``tt_matvec``): forward the chain of ``ttr_ttm_step``, the step inputs kept for the cores
+  that need a gradient; backward one ``ttr_ttm_grad_core`` per such core and one ``ttr_ttm_grad_input`` per step that still has
+  an operand before it which needs one, each step's ``dX`` being the previous step's ``dY`` as it lies;
 - ``mode_mul`` (Tucker factors), ``gemm`` (the chain of ``Tensor.torch()``) and ``dense_dist`` (``tn.dist`` /
   ``tn.relative_error`` against a dense tensor): existing kernels in both directions.
 
@@ -275,6 +279,55 @@ def dense_dist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     if a.numel() != b.numel():
         raise ValueError("dist: the operands have {} and {} elements".format(a.numel(), b.numel()))
     return _DenseDist.apply(a, b)
+
+
+# ---------------------------------------------------------------------------------------------- tt_multiply
+class _TTMatvec(torch.autograd.Function):
+    """y [b, cols] = x2d [b, rows] times the TT-matrix with the cores G_k [r_k, I_k, O_k, r_{k+1}] (r_0 = r_d = 1), through the
+    three step functions of ``ops`` (``_hipops`` or ``_hostops``).  X_k [I_k, D_k, r_k] and Y_{k-1} [D_{k-1}, O_{k-1}, r_k] are
+    the same memory, so a contiguous dX_k is dY_{k-1} as it lies: the backward chain copies nothing but ``dx``, transposed."""
+
+    @staticmethod
+    def forward(ctx, ops, x2d, *cores):
+        needs = [bool(n) for n in ctx.needs_input_grad[2:]]
+        X = x2d.t().contiguous()  # (grad mode is off in here: x2d and the cores still carry requires_grad, nothing is recorded)
+        kept = []
+        for G, need in zip(cores, needs):
+            X = X.view(G.shape[1], -1, G.shape[0])
+            kept.append(X if need else None)  # X_k is needed by dG_k only
+            X = ops.ttm_step(X, G)
+        ctx.ops = ops
+        ctx.save_for_backward(*cores, *kept)
+        return X.view(x2d.shape[0], -1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        ops = ctx.ops
+        d = len(ctx.saved_tensors) // 2
+        cores, kept = ctx.saved_tensors[:d], ctx.saved_tensors[d:]
+        need_x, needs = bool(ctx.needs_input_grad[1]), [bool(n) for n in ctx.needs_input_grad[2:]]
+        grads: List[Optional[torch.Tensor]] = [None] * d
+        b = g.shape[0]
+        dY = g.contiguous()  # [b, cols] is dY_{d-1} [D_{d-1}, O_{d-1}, 1] as it lies
+        for k in range(d - 1, -1, -1):
+            G = cores[k]
+            dY = dY.view(-1, G.shape[2], G.shape[3])
+            if needs[k]:
+                grads[k] = ops.ttm_grad_core(kept[k], dY)
+            if not (need_x or any(needs[:k])):  # nothing earlier needs a gradient: the chain ends here
+                break
+            dY = ops.ttm_grad_input(dY, G)  # dX_k [I_k, D_k, r_k]: dY_{k-1}
+        dx = dY.view(-1, b).t().contiguous() if need_x else None  # dX_0 is [rows, b]: the one transposed copy, as at entry
+        return (None, dx) + tuple(grads)
+
+
+def tt_matvec(cores: Sequence[torch.Tensor], x2d: torch.Tensor, ops) -> torch.Tensor:
+    """Differentiable ``x2d [b, rows] @ M -> [b, cols]`` for TT-matrix cores [r_k, I_k, O_k, r_{k+1}] with boundary ranks 1.
+    ``ops`` supplies ``ttm_step``, ``ttm_grad_input`` and ``ttm_grad_core``.  The forward is the chain of
+    ``tt_matvec_chain`` (the same launches, the same bits); the backward launches one ``ttm_grad_core`` per core that requires
+    grad and one ``ttm_grad_input`` per step with an operand before it that does."""
+    return _TTMatvec.apply(ops, x2d, *cores)
 
 
 # ---------------------------------------------------------------------------------------------- autodiff.py:10-121

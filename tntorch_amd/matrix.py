@@ -12,8 +12,11 @@ tensors the streaming right-to-left TT-SVD kernels -- and every core ``[r, i_k o
 as it lies, so on the device the chain is ``d`` launches of ``ttr_ttm_step`` and one transposed copy of ``x`` at entry;
 ``cp_multiply`` is the same chain with the rank carried (``ttr_cpm_step``) and summed at the end (``ttr_mode_reduce``).
 Unlike the reference, both check their operands and raise ``ValueError`` (the reference fails an ``assert`` or inside einsum).
+``tt_multiply`` is differentiable on the device in the cores and in the tensor (``autodiff.tt_matvec``: two fused backward
+kernels per step, ``ttr_ttm_grad_core`` and ``ttr_ttm_grad_input``); ``cp_multiply`` is not, and says so.
 Not here: ``determinant`` / ``slog_determinant`` / ``inv`` / ``cholesky`` (the reference's own guard raises for every square
-matrix, so none of them can run there), the transposed product and autograd through the device kernels.
+matrix, so none of them can run there), the transposed product as a public call and autograd through ``cp_multiply`` on the
+device.
 """
 
 from __future__ import annotations
@@ -212,20 +215,30 @@ def _multiply_operands(who: str, kind, matrix, tensor: torch.Tensor, core_dims: 
 def tt_multiply(tt_matrix: TTMatrix, tensor: torch.Tensor) -> torch.Tensor:
     """``tensor.reshape(b, rows) @ tt_matrix.torch()`` -> ``[b, cols]`` on the operands' device in their dtype, without forming
     the matrix (matrix.py:420-443): ``d`` steps, on the device one ``ttr_ttm_step`` launch each.  ``tensor`` has at least 2
-    dimensions and a multiple of ``rows`` elements (a vector is ``[1, rows]``); neither operand is modified."""
+    dimensions and a multiple of ``rows`` elements (a vector is ``[1, rows]``); neither operand is modified.  With grad mode on
+    and a device core or tensor that requires grad the result carries a backward pass (``autodiff.tt_matvec``): the same forward
+    launches and bits, then one ``ttr_ttm_grad_core`` per core and one ``ttr_ttm_grad_input`` per step that need a gradient."""
     x2d, cols = _multiply_operands("tt_multiply", TTMatrix, tt_matrix, tensor, 4)
     cores = tt_matrix.cores
     if cores[0].shape[0] != 1 or cores[-1].shape[-1] != 1:
         raise ValueError("tt_multiply: the boundary ranks must be 1, got {} and {}".format(cores[0].shape[0], cores[-1].shape[-1]))
     if x2d.shape[0] == 0:
         return torch.zeros((0, cols), dtype=tensor.dtype, device=tensor.device)
+    if x2d.device.type != "cpu" and torch.is_grad_enabled() and (x2d.requires_grad or any(c.requires_grad for c in cores)):
+        from . import autodiff
+
+        return autodiff.tt_matvec(cores, x2d, ops_for(x2d, grad=True))
     return ops_for(x2d).tt_matvec_chain(cores, x2d)
 
 
 def cp_multiply(cp_matrix: CPMatrix, tensor: torch.Tensor) -> torch.Tensor:
     """``tensor.reshape(b, rows) @ cp_matrix.torch()`` -> ``[b, cols]`` (matrix.py:446-468): ``d`` steps that carry the rank
-    index, on the device one ``ttr_cpm_step`` launch each, and the sum over the rank (``ttr_mode_reduce``)."""
+    index, on the device one ``ttr_cpm_step`` launch each, and the sum over the rank (``ttr_mode_reduce``).  Not differentiable
+    on the device: under grad mode an operand there that requires grad raises ``NotImplementedError``."""
     x2d, cols = _multiply_operands("cp_multiply", CPMatrix, cp_matrix, tensor, 3)
     if x2d.shape[0] == 0:
         return torch.zeros((0, cols), dtype=tensor.dtype, device=tensor.device)
+    if x2d.device.type != "cpu" and torch.is_grad_enabled() and any(c.requires_grad for c in cp_matrix.cores):
+        # (a tensor that requires grad is refused by ops_for; cores that do would come back detached, silently)
+        raise NotImplementedError("tntorch_amd: cp_multiply is not differentiable on the device; detach the cores or use CPU tensors")
     return ops_for(x2d).cp_matvec_chain(cp_matrix.cores, x2d)
