@@ -56,7 +56,7 @@ extern "C" {
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
    ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
-   ttr_ttm_grad_core.  ttr_version() returns the value the library was built with; the Python
+   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1192,6 +1192,42 @@ int64_t ttr_ttm_grad_core_slab_rows(int dtype, int64_t I, int64_t D, int64_t R, 
 int64_t ttr_ttm_grad_core_workspace_bytes(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S);
 int ttr_ttm_grad_core(int dtype, int64_t I, int64_t D, int64_t R, int64_t O, int64_t S, const void* X, const void* dY, void* dG,
                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * One step of the row lookup of a TT-matrix, M[rows, :] without the dense matrix (added under ABI 17; lookup.py `tt_lookup`;
+ * DESIGN section 27):
+ *
+ *   Y[p, dd, o, s] = sum_r X[xrow ? xrow[p] : p, dd, r] * G[r, idx[p], o, s]
+ *
+ * `X` [rows_x, D, R] and `Y` [P, D, O, S] are contiguous; Y of a step, read as [P, D O, S], is the X of the next one as it lies.
+ * `G` [R, I, O, S] (a TTMatrix core) has the four element strides g_strides, a HOST array: a unit stride along S and no negative
+ * stride are needed (else TTR_E_UNSUPPORTED before a byte is read; the stride of an extent-1 axis is free), so a sliced or
+ * permuted view of a core is read where it lies.  `idx` and `xrow` are int64 device vectors of P entries, BOTH with the element
+ * stride `stride_idx`: two columns of one [P, d] digit table (stride d), or two contiguous vectors (stride 1).  `xrow` may be
+ * NULL: sample p then reads X[p].  idx wraps negative values as in torch (-I <= idx < I); xrow does not (0 <= xrow < rows_x).
+ *
+ * The indices are validated on the device first: a bad entry ORs the int32 device word *oob_flag with 1, and then nothing else is
+ * written.  The word is NOT cleared by the call -- the steps of a chain share one word, cleared by the caller before the first
+ * and read after the last -- and when it is set on entry the call writes nothing.  No host synchronisation.
+ *
+ * The samples are grouped by idx on the device (a counting sort: histogram, scan, scatter of the sample ids into `workspace`;
+ * ttr_ttm_lookup_workspace_bytes(P, I) bytes, < 0 for P < 0 or an I outside 1 .. 2^31 - 1), so that the samples of a group share
+ * their R x (O S) slice: a workgroup owns 64 (sample, dd) rows x 64 columns of one group, stages the gathered X rows and the
+ * slice through LDS in chunks of 32 r and multiplies on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 (operands and
+ * accumulators in the dtype).  Rows past the group, column tiles of 16 past O S and quads of r past R are zero-filled in LDS or
+ * skipped, never read out of bounds.  Every element of Y is one accumulation chain in increasing r whose order depends on R and
+ * the dtype alone: a row's bits do not depend on P, on the other samples, on the order inside a group or on xrow being NULL or
+ * the identity.  No atomics on floating-point data.  No rank limit, 64-bit element offsets.  Profiling kind: TTR_PROF_GEMM.
+ *
+ * Before any launch, with Y untouched: TTR_E_INVALID for a bad dtype, an extent < 1 (P = 0 returns TTR_OK at once), a
+ * stride_idx < 1, a null pointer (xrow excepted) or a Y that is one of the inputs; TTR_E_UNSUPPORTED for the strides of G above,
+ * for D R, O S, P D, I or rows_x above 2^31 - 1 and for an operand of 2^57 elements or more; TTR_E_WORKSPACE for a missing or
+ * short workspace.
+ */
+int64_t ttr_ttm_lookup_workspace_bytes(int64_t P, int64_t I);
+int ttr_ttm_lookup_step(int dtype, int64_t P, int64_t rows_x, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S,
+                        const void* X, const void* xrow, const void* G, const int64_t* g_strides, const void* idx,
+                        int64_t stride_idx, void* Y, void* oob_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

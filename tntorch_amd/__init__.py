@@ -16,7 +16,8 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ``tn.sum`` / ``tn.mean``), and the variance-based sensitivity analysis of ``anova.py``: ``tn.anova_decomposition``,
 ``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``,
 and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``, and the matrix formats of
-``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``, and gradient-based fitting (``autodiff.py``):
+``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``, and a batch of rows of a TT-matrix
+(``tn.tt_lookup``: the embedding table), and gradient-based fitting (``autodiff.py``):
 ``tn.optimize`` and ``tn.dof``, with ``t[X]`` at index arrays, ``Tensor.torch()``, ``tn.dist`` / ``tn.relative_error`` against a
 dense tensor and ``tn.tt_multiply`` (in the cores and the tensor) differentiable on the device (hand-written backward passes; every other operation refuses device cores that require
 grad).
@@ -28,6 +29,7 @@ from .tensor import *  # noqa: F401,F403
 from .create import *  # noqa: F401,F403
 from .metrics import *  # noqa: F401,F403
 from .matrix import *  # noqa: F401,F403
+from .lookup import *  # noqa: F401,F403
 from .maxvol import *  # noqa: F401,F403
 from .cross import *  # noqa: F401,F403
 from .ops import *  # noqa: F401,F403
@@ -37,7 +39,7 @@ from .automata import *  # noqa: F401,F403
 from .logic import *  # noqa: F401,F403
 from .anova import *  # noqa: F401,F403
 from .autodiff import *  # noqa: F401,F403
-from . import autodiff, automata, logic  # noqa: F401
+from . import autodiff, automata, logic, lookup  # noqa: F401
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

@@ -1709,3 +1709,43 @@ def ttm_grad_core(X: torch.Tensor, dY: torch.Tensor, out: Optional[torch.Tensor]
     _call("ttr_ttm_grad_core", dt, I, D, R, O, S, X.data_ptr(), dY.data_ptr(), out.data_ptr(), _ptr(ws),
           int(ws.numel()) if ws is not None else 0)
     return out
+
+
+def ttm_lookup_workspace_bytes(P: int, I: int) -> int:
+    """Bytes of workspace ttr_ttm_lookup_step needs for P samples and a mode of size I (the grouping of the samples)."""
+    wsb = int(lib().ttr_ttm_lookup_workspace_bytes(int(P), int(I)))
+    if wsb < 0:
+        _check(wsb, "ttr_ttm_lookup_workspace_bytes")
+    return wsb
+
+
+@_on_device
+def ttm_lookup_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tensor, idx: torch.Tensor, flag: torch.Tensor,
+                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ttm_lookup_step: Y[p, dd, o, s] = sum_r X[xrow[p], dd, r] G[r, idx[p], o, s] for a contiguous X [rows_x, D, R], G
+    [R, I, O, S] (a TTMatrix core, passed with the strides it has: the library wants a unit last stride) and int64 device vectors
+    ``idx`` and ``xrow`` (or None: X[p]) of P entries WITH THE SAME STRIDE (two columns of one digit table, or two contiguous
+    vectors) -> Y [P, D, O, S].  ``idx`` wraps negative values, ``xrow`` does not.  Nothing is read back: a bad entry ORs the
+    int32 device word ``flag`` and leaves Y unwritten, and so does a word that is set on entry; the word is never cleared here.
+    ``out``: a contiguous tensor of P D O S elements; ``workspace``: uint8, at least ``ttm_lookup_workspace_bytes(P, I)``."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and G.dim() == 4 and G.dtype == X.dtype and G.device == X.device and X.is_contiguous()
+    rows_x, D, R = X.shape
+    assert G.shape[0] == R
+    I, O, S = G.shape[1], G.shape[2], G.shape[3]
+    assert idx.dim() == 1 and idx.dtype == torch.int64 and idx.device == X.device
+    P = idx.shape[0]
+    stride = int(idx.stride(0)) if P > 1 else 1
+    if xrow is not None:
+        assert xrow.dtype == torch.int64 and tuple(xrow.shape) == (P,) and xrow.device == X.device
+        assert P <= 1 or int(xrow.stride(0)) == stride, "ttm_lookup_step: idx and xrow must have the same stride"
+    assert flag.dtype == torch.int32 and flag.numel() == 1 and flag.device == X.device
+    if out is None:
+        out = torch.empty((P, D, O, S), dtype=X.dtype, device=X.device)
+    assert out.numel() == P * D * O * S and out.is_contiguous() and out.dtype == X.dtype and out.device == X.device
+    if P == 0:
+        return out
+    ws = workspace if workspace is not None else _workspace(ttm_lookup_workspace_bytes(P, I), X.device)
+    _call("ttr_ttm_lookup_step", dt, P, rows_x, D, R, I, O, S, X.data_ptr(), _ptr(xrow), G.data_ptr(), _i64(G.stride()),
+          idx.data_ptr(), stride, out.data_ptr(), flag.data_ptr(), ws.data_ptr(), int(ws.numel()))
+    return out

@@ -2292,3 +2292,34 @@ def cp_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.T
         X = _hip.cpm_step(X.view(I, -1) if k == 0 else X.view(I, -1, R), C.contiguous())
     R = cores[-1].shape[2]
     return _hip.mode_reduce(X.view(-1, R, 1)).view(b, -1)
+
+
+# ---------------------------------------------------------------------------------------------- TT-matrix row lookup (lookup.py)
+def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torch.Tensor:
+    """Rows ``rows1d`` [P] (an integer device vector) of the TT-matrix with the cores G_k [r_k, I_k, O_k, r_{k+1}] -> [P, prod
+    O_k].  The digit table [P, d] (int64) comes from a handful of torch ops; d = 1 is an ``index_select``; d >= 2 is d - 1
+    launches of ttr_ttm_lookup_step that read columns of the table with its stride: the first launch reads G_1 itself, viewed as
+    [I_1, O_1, r_1], through the row map xrow = i_1 (no per-sample copy of the first core), and the output of a launch is the
+    input of the next as it lies.  Only a step's input and output are alive at a time.  A row outside [-rows, rows) has a first
+    digit outside its mode: the launches' shared flag word (d = 1: a torch comparison) is read once at the end -- the only
+    host synchronisation -- and IndexError is raised instead of a result."""
+    P = rows1d.shape[0]
+    dev = cores[0].device
+    digits = _hostops.lookup_digits(cores, rows1d)
+    G1 = cores[0][0]                                               # [I_1, O_1, r_1]
+    if len(cores) == 1:
+        i1 = digits[:, 0]
+        flag = ((i1 < 0) | (i1 >= G1.shape[0])).any()
+        out = torch.index_select(G1[:, :, 0], 0, i1.clamp(0, G1.shape[0] - 1))
+    else:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _hip._workspace(max(_hip.ttm_lookup_workspace_bytes(P, int(G.shape[1])) for G in cores[1:]), dev)
+        X, xrow = G1.contiguous(), digits[:, 0]
+        for k in range(1, len(cores)):
+            G = cores[k].contiguous()
+            X = _hip.ttm_lookup_step(X.view(X.shape[0], -1, G.shape[0]), xrow, G, digits[:, k], flag, workspace=ws)
+            xrow = None
+        out = X.view(P, -1)
+    if bool(flag.item()):  # the one host read of the call
+        raise IndexError("tt_lookup: a row index lies outside the matrix")
+    return out

@@ -974,3 +974,39 @@ def cp_matvec_chain(cores: Sequence[torch.Tensor], x2d: torch.Tensor) -> torch.T
         Xk = X.reshape(I, -1, 1) if k == 0 else X.reshape(I, -1, R)
         X = (Xk[:, :, None, :] * C[:, None, :, :]).sum(dim=0)
     return X.sum(dim=-1).reshape(b, -1)
+
+
+# ---------------------------------------------------------------------------------------------- TT-matrix row lookup (lookup.py)
+def lookup_digits(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torch.Tensor:
+    """The int64 [P, d] digit table of the rows: row j (negative: j + rows) splits row-major over the input modes, i_1 most
+    significant.  Digits 2 .. d are reduced modulo their mode; the FIRST is not, so a row outside [-rows, rows) shows as a first
+    digit outside 0 .. I_1 - 1 (below 0 for a row below -rows) and nowhere else."""
+    sizes = [int(c.shape[1]) for c in cores]
+    total = 1
+    for n in sizes:
+        total *= n
+    j = rows1d.to(torch.int64)
+    j = torch.where(j < 0, j + total, j)
+    cols, below = [], total
+    for k, n in enumerate(sizes):
+        below //= n
+        q = torch.div(j, below, rounding_mode="floor")
+        cols.append(q if k == 0 else q % n)
+    return torch.stack(cols, dim=1)
+
+
+def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torch.Tensor:
+    """Rows ``rows1d`` [P] of the TT-matrix with the cores G_k [r_k, I_k, O_k, r_{k+1}] (r_0 = r_d = 1) -> [P, prod O_k]: the
+    chain of ttr_ttm_lookup_step in torch ops.  Z_1 = G_1[0, i_1] [P, O_1, r_1]; step k contracts r of Z_{k-1} [P, D, r] with
+    the slice G_k[:, i_k(p)] of every sample, and its output [P, D, O_k, r_k], row-major, is Z_k [P, D O_k, r_k].  Plain torch, so
+    differentiable in the cores.  IndexError for a row outside [-rows, rows)."""
+    P = rows1d.shape[0]
+    digits = lookup_digits(cores, rows1d)
+    i1 = digits[:, 0]
+    if bool(((i1 < 0) | (i1 >= cores[0].shape[1])).any()):
+        raise IndexError("tt_lookup: a row index lies outside the matrix")
+    Z = cores[0][0][i1]                                            # [P, O_1, r_1]
+    for k in range(1, len(cores)):
+        Gk = cores[k][:, digits[:, k]]                             # [R, P, O, S]
+        Z = torch.einsum("pdr,rpos->pdos", Z, Gk).reshape(P, -1, Gk.shape[3])
+    return Z.reshape(P, -1)
