@@ -56,7 +56,7 @@ extern "C" {
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
    ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
-   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step.  ttr_version() returns the value the library was built with; the Python
+   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1228,6 +1228,32 @@ int64_t ttr_ttm_lookup_workspace_bytes(int64_t P, int64_t I);
 int ttr_ttm_lookup_step(int dtype, int64_t P, int64_t rows_x, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S,
                         const void* X, const void* xrow, const void* G, const int64_t* g_strides, const void* idx,
                         int64_t stride_idx, void* Y, void* oob_flag, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * One core of a TT-matrix product that stays in TT format (added under ABI 17; ttalgebra.py `tt_apply`, `tt_matmul`; DESIGN
+ * section 28):
+ *     out[r S1 + a, p, q, s S2 + b] = sum_j A[r, p, j, s] B[a, j, q, b]
+ * `A` [R1, P, J, R2], `B` [S1, J, Q, S2] and `out` [R1 S1, P, Q, R2 S2] are contiguous; the rank layout is ttr_core_kron's (the
+ * first operand's rank major).  P = 1 is a core of vec(t) @ M (A the train's core, B the matrix core), Q = 1 one of M @ vec(u),
+ * the general case one of the product of two TT-matrices.  A GEMM with M = (r, p, s), N = (a, q, b) and K = J whose output, E =
+ * R1 S1 P Q R2 S2 elements, is written once for 2 J E flops while the small operands are re-read from the cache: a store kernel
+ * for the J of a mode.  A workgroup owns TTR_COMPOSE_TILE_M rows x TTR_COMPOSE_TILE_N columns (s resp. b fastest) and walks J in
+ * chunks of TTR_COMPOSE_TILE_K through LDS, on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 (operands and accumulators in
+ * the dtype; quads of j, the tail zero-filled).  The accumulators are staged through LDS and written in memory order --
+ * (segment of equal (a, q), row, b): consecutive lanes are consecutive addresses along the runs of R2 S2 elements a fixed
+ * (r, a, p, q) has -- in 16-byte packs where S2 is a multiple of 16 bytes of elements (every row of a run then starts on a
+ * pack) and `out` is 16-byte aligned, else in scalar stores with the same arithmetic and order.  Every element is one
+ * accumulation chain from 0 in increasing j: its bits do not depend on its place in a tile, on the other extents or on the
+ * alignment of `out`.  Every element is written exactly once; no atomics, no workspace, no rank limit, 64-bit element offsets.
+ * Before any launch, `out` untouched: TTR_E_INVALID for a bad dtype, an extent < 1, a null pointer or out == A / out == B;
+ * TTR_E_UNSUPPORTED only where an extent, a rank product (R1 S1, R2 S2) or the number of workgroups does not fit 32 bits, or
+ * an operand has 2^57 elements or more.  Profiling kind: TTR_PROF_GEMM.
+ */
+#define TTR_COMPOSE_TILE_M 64
+#define TTR_COMPOSE_TILE_N 64
+#define TTR_COMPOSE_TILE_K 32
+int ttr_core_compose(int dtype, int64_t R1, int64_t P, int64_t J, int64_t R2, int64_t S1, int64_t Q, int64_t S2, const void* A,
+                     const void* B, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,8 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``,
 and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``, and the matrix formats of
 ``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``, and a batch of rows of a TT-matrix
-(``tn.tt_lookup``: the embedding table), and gradient-based fitting (``autodiff.py``):
+(``tn.tt_lookup``: the embedding table), and the products that stay in TT format (``tn.tt_apply``: a TT-matrix applied to a
+train, ``tn.tt_matmul``, ``tn.tt_transpose``), and gradient-based fitting (``autodiff.py``):
 ``tn.optimize`` and ``tn.dof``, with ``t[X]`` at index arrays, ``Tensor.torch()``, ``tn.dist`` / ``tn.relative_error`` against a
 dense tensor and ``tn.tt_multiply`` (in the cores and the tensor) differentiable on the device (hand-written backward passes; every other operation refuses device cores that require
 grad).
@@ -30,6 +31,7 @@ from .create import *  # noqa: F401,F403
 from .metrics import *  # noqa: F401,F403
 from .matrix import *  # noqa: F401,F403
 from .lookup import *  # noqa: F401,F403
+from .ttalgebra import *  # noqa: F401,F403
 from .maxvol import *  # noqa: F401,F403
 from .cross import *  # noqa: F401,F403
 from .ops import *  # noqa: F401,F403

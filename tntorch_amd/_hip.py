@@ -1520,6 +1520,31 @@ def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Te
     return out
 
 
+@_on_device
+def core_compose(A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_core_compose: A [R1, P, J, R2], B [S1, J, Q, S2] (contiguous) -> [R1 S1, P, Q, R2 S2] with
+    out[r S1 + a, p, q, s S2 + b] = sum_j A[r, p, j, s] B[a, j, q, b]: one core of a TT-matrix product that stays in TT format.
+    ValueError for anything but two contiguous 4-d device cores of one dtype with the same J.  ``out``: a contiguous tensor of
+    that many elements which receives the result (wherever it lies: the bits do not depend on its alignment); fresh when None."""
+    if A.dim() != 4 or B.dim() != 4 or A.dtype != B.dtype or A.device != B.device or not A.is_cuda:
+        raise ValueError("core_compose: expected two 4-d cores of one dtype on one device")
+    if A.shape[2] != B.shape[1]:
+        raise ValueError("core_compose: A [R1, P, J, R2] and B [S1, J, Q, S2] need the same J, got {} and {}".format(A.shape[2], B.shape[1]))
+    if not (A.is_contiguous() and B.is_contiguous()):
+        raise ValueError("core_compose: the cores must be contiguous")
+    dt = dtype_code(A.dtype)
+    R1, P, J, R2 = A.shape
+    S1, _, Q, S2 = B.shape
+    shape = (R1 * S1, P, Q, R2 * S2)
+    if out is None:
+        out = torch.empty(shape, dtype=A.dtype, device=A.device)
+    if not (out.numel() == R1 * S1 * P * Q * R2 * S2 and out.is_contiguous() and out.dtype == A.dtype and out.device == A.device):
+        raise ValueError("core_compose: out must be a contiguous tensor of {} elements of the cores' dtype on their device".format(
+            R1 * S1 * P * Q * R2 * S2))
+    _call("ttr_core_compose", dt, R1, P, J, R2, S1, Q, S2, A.data_ptr(), B.data_ptr(), out.data_ptr())
+    return out.view(shape)
+
+
 def accept_max_rank() -> int:
     """ttr_accept_max_rank: the largest rank ttr_accept_count / ttr_accept_expand take."""
     return int(lib().ttr_accept_max_rank())

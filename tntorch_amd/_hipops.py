@@ -1879,6 +1879,13 @@ def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Te
     return _hip.core_convolve(a.contiguous(), c.contiguous(), lo, K)
 
 
+def core_compose(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """One core of a TT-matrix product that stays in TT format (ttr_core_compose): A [R1, P, J, R2], B [S1, J, Q, S2] ->
+    [R1 S1, P, Q, R2 S2], out[r S1 + a, p, q, s S2 + b] = sum_j A[r, p, j, s] B[a, j, q, b].  Views (a transposed matrix core, a
+    train core with an inserted axis) are made contiguous first: the kernel has no strided path."""
+    return _hip.core_compose(A.contiguous(), B.contiguous())
+
+
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1, C4)
 def _sum_all(x: torch.Tensor) -> torch.Tensor:
     """Sum of all entries as a 1 x n x 1 GEMM with a ones vector (split-K); returns a 0-d tensor."""

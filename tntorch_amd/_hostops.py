@@ -577,6 +577,18 @@ def core_convolve(a: torch.Tensor, c: torch.Tensor, lo: int, K: int) -> torch.Te
     return out.reshape(R1 * S1, K, R2 * S2)
 
 
+def core_compose(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """Mirror of ttr_core_compose: A [R1, P, J, R2], B [S1, J, Q, S2] -> [R1 S1, P, Q, R2 S2],
+    out[r S1 + a, p, q, s S2 + b] = sum_j A[r, p, j, s] B[a, j, q, b].  One einsum in the input dtype: differentiable."""
+    if A.dim() != 4 or B.dim() != 4 or A.dtype != B.dtype or A.device != B.device:
+        raise ValueError("core_compose: expected two 4-d cores of one dtype on one device")
+    if A.shape[2] != B.shape[1]:
+        raise ValueError("core_compose: A [R1, P, J, R2] and B [S1, J, Q, S2] need the same J, got {} and {}".format(A.shape[2], B.shape[1]))
+    R1, P, _, R2 = A.shape
+    S1, _, Q, S2 = B.shape
+    return torch.einsum("rpjs,ajqb->rapqsb", A, B).reshape(R1 * S1, P, Q, R2 * S2)
+
+
 # ---------------------------------------------------------------------------------------------- CP-ALS (SURVEY 8f-1)
 def cp_als(X: torch.Tensor, R: int, max_iter: int, tol: float, verbose: bool = False, batch: bool = False, init=None):
     """tensor.py:210-400, the reference's operator sequence on the CPU.  ``init=None``: HOSVD initialisation
