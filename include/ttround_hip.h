@@ -56,7 +56,7 @@ extern "C" {
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
    ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
-   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose.  ttr_version() returns the value the library was built with; the Python
+   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose, and ttr_env_half_apply.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1254,6 +1254,37 @@ int ttr_ttm_lookup_step(int dtype, int64_t P, int64_t rows_x, int64_t D, int64_t
 #define TTR_COMPOSE_TILE_K 32
 int ttr_core_compose(int dtype, int64_t R1, int64_t P, int64_t J, int64_t R2, int64_t S1, int64_t Q, int64_t S2, const void* A,
                      const void* B, void* out, void* stream);
+
+/*
+ * Half of a three-layer environment application, the hot path of the ALS solver (added under ABI 17; ttsolve.py `tt_solve`;
+ * DESIGN section 29):
+ *     H[r, i, a', s'] = sum_{a, j} G[a, i, j, a'] * ( sum_{r'} Phi[r, a, r'] * X[r', j, s'] )
+ * `Phi` [R, A, R'] (an interface of bra, matrix and ket) and `H` [R, I, A', S'] are contiguous.  `X` [R', J, S'] (a ket core) has
+ * the three element strides x_strides and `G` [A, I, J, A'] (a TT-matrix core) the four element strides g_strides, both HOST
+ * arrays: any non-negative strides are read where they lie (a tt_transpose view, the rank-swapped views of a right-to-left
+ * sweep); a negative stride, or strides that span 2^57 elements or more, are TTR_E_UNSUPPORTED before a byte is read, and the
+ * stride of an extent-1 axis is free.
+ * With H laid out this way both of its consumers are plain ttr_gemm calls on H as it lies: the local matvec
+ * y[r, i, s] = sum_{a', s'} H[r, i, a', s'] Psi[s, a', s'] (M = R I, K = A' S', N = S, second operand transposed) and the
+ * environment update Phi'[s, a', s'] = sum_{r, i} Y[r, i, s] H[r, i, a', s'] (first operand transposed).
+ * The intermediate T[r, (a, j), s'] never reaches global memory: a workgroup owns TTR_ENV_TILE_R r x TTR_ENV_TILE_S s' x
+ * TTR_ENV_TILE_N columns (i, a') of H, walks k = a J + j in chunks of TTR_ENV_TILE_K, computes the chunk's T tiles (sums over r',
+ * operands straight from memory) into LDS and multiplies them with the staged chunk of G; both contractions run on
+ * v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 with operands and accumulators in the dtype.  Stage 1 is recomputed once per
+ * column tile.  Everything past an extent is a zero in LDS or is skipped, never read.  No workspace, no atomics, no split of
+ * either sum across workgroups, no rank limit, 64-bit element offsets.  Every element of H is one chain -- the inner sums from 0
+ * in increasing r', the outer from 0 in increasing (a, j) -- fixed by R', A, J and the dtype: the same call gives the same bits,
+ * and an element's bits do not depend on its place in a tile or on R, S', I, A'.
+ * Before any launch, with H untouched: TTR_E_INVALID for a bad dtype, an extent < 1, a null pointer or an H that is one of the
+ * inputs; TTR_E_UNSUPPORTED for the strides above, for an extent, A J, I A' or a number of workgroups beyond 2^31 - 1 and for an
+ * operand of 2^57 elements or more.  Profiling kind: TTR_PROF_GEMM.
+ */
+#define TTR_ENV_TILE_R 16
+#define TTR_ENV_TILE_S 16
+#define TTR_ENV_TILE_N 64
+#define TTR_ENV_TILE_K 16
+int ttr_env_half_apply(int dtype, int64_t R, int64_t A, int64_t Rp, int64_t J, int64_t Sp, int64_t I, int64_t Ap, const void* Phi,
+                       const void* X, const int64_t* x_strides, const void* G, const int64_t* g_strides, void* H, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1774,3 +1774,34 @@ def ttm_lookup_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tens
     _call("ttr_ttm_lookup_step", dt, P, rows_x, D, R, I, O, S, X.data_ptr(), _ptr(xrow), G.data_ptr(), _i64(G.stride()),
           idx.data_ptr(), stride, out.data_ptr(), flag.data_ptr(), ws.data_ptr(), int(ws.numel()))
     return out
+
+
+@_on_device
+def env_half_apply(Phi: torch.Tensor, X: torch.Tensor, G: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_env_half_apply: Phi [R, A, R'] (contiguous), X [R', J, S'] and G [A, I, J, A'] (both passed with the strides they have:
+    a tt_transpose view or a rank-swapped view is read where it lies; the library refuses negative strides with
+    NotImplementedError) -> H [R, I, A', S'] with H[r, i, c, s] = sum_{a, j} G[a, i, j, c] sum_b Phi[r, a, b] X[b, j, s].
+    ValueError for anything but device tensors of one dtype whose extents fit.  ``out``: a contiguous tensor of R I A' S'
+    elements that receives the result; fresh when None."""
+    if Phi.dim() != 3 or X.dim() != 3 or G.dim() != 4 or not Phi.is_cuda:
+        raise ValueError("env_half_apply: expected device tensors Phi [R, A, R'], X [R', J, S'] and G [A, I, J, A']")
+    if not (X.dtype == Phi.dtype and G.dtype == Phi.dtype and X.device == Phi.device and G.device == Phi.device):
+        raise ValueError("env_half_apply: the operands must have one dtype and lie on one device")
+    dt = dtype_code(Phi.dtype)
+    R, A, Rp = Phi.shape
+    _, J, Sp = X.shape
+    _, I, _, Ap = G.shape
+    if X.shape[0] != Rp or G.shape[0] != A or G.shape[2] != J:
+        raise ValueError("env_half_apply: Phi {}, X {} and G {} do not fit together".format(
+            tuple(Phi.shape), tuple(X.shape), tuple(G.shape)))
+    if not Phi.is_contiguous():
+        raise ValueError("env_half_apply: Phi must be contiguous")
+    shape = (R, I, Ap, Sp)
+    if out is None:
+        out = torch.empty(shape, dtype=Phi.dtype, device=Phi.device)
+    if not (out.numel() == R * I * Ap * Sp and out.is_contiguous() and out.dtype == Phi.dtype and out.device == Phi.device):
+        raise ValueError("env_half_apply: out must be a contiguous tensor of {} elements of the operands' dtype on their device".format(
+            R * I * Ap * Sp))
+    _call("ttr_env_half_apply", dt, R, A, Rp, J, Sp, I, Ap, Phi.data_ptr(), X.data_ptr(), _i64(X.stride()), G.data_ptr(),
+          _i64(G.stride()), out.data_ptr())
+    return out.view(shape)

@@ -2330,3 +2330,55 @@ def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torc
     if bool(flag.item()):  # the one host read of the call
         raise IndexError("tt_lookup: a row index lies outside the matrix")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- tt_solve (ttsolve.py)
+def gemm2d(A: torch.Tensor, B: torch.Tensor, transA: bool = False, transB: bool = False) -> torch.Tensor:
+    """op(A) @ op(B) of two matrices on ttr_gemm."""
+    return _hip.gemm(A[None], B[None], transA=transA, transB=transB)[0]
+
+
+def env_half_apply(Phi: torch.Tensor, X: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """H[r, i, c, s] = sum_{a, j} G[a, i, j, c] sum_b Phi[r, a, b] X[b, j, s]: Phi [R, A, R'], X [R', J, S'], G [A, I, J, A'] ->
+    H [R, I, A', S'], one launch of ttr_env_half_apply.  X and G are read with the strides they have; the kernel has no size
+    limit, so there is no other route."""
+    return _hip.env_half_apply(Phi if Phi.is_contiguous() else Phi.contiguous(), X, G)
+
+
+def env_half_apply_unfused(Phi: torch.Tensor, X: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """The same H built from the kernels the library had before: ttr_gemm (the sum over r'), a permuted copy, ttr_ttm_step (the sum
+    over (a, j)) and a second permuted copy.  The intermediate [R, A, J, S'] goes through memory twice.  What
+    tools/solve_bench.py measures ttr_env_half_apply against; nothing calls it on the solver's path."""
+    R, A, Rp = Phi.shape
+    _, J, Sp = X.shape
+    _, I, _, Ap = G.shape
+    T = gemm2d(Phi.reshape(R * A, Rp), X.contiguous().reshape(Rp, J * Sp))                   # [(r, a), (j, s')]
+    Xin = T.reshape(R, A, J, Sp).permute(2, 0, 3, 1).contiguous().reshape(J, R * Sp, A)     # [j, (r, s'), a]
+    Y = _hip.ttm_step(Xin, G.permute(0, 2, 1, 3).contiguous())                               # [(r, s'), i, a']
+    return Y.reshape(R, Sp, I, Ap).permute(0, 2, 3, 1).contiguous()
+
+
+def local_matvec(Phi: torch.Tensor, G: torch.Tensor, Psi: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """y[r, i, s] = sum Phi[r, a, b] G[a, i, j, c] Psi[s, c, t] v[b, j, t]: ttr_env_half_apply and one ttr_gemm on H as it lies."""
+    H = env_half_apply(Phi, v, G)
+    R, I, Ap, Sp = H.shape
+    S = Psi.shape[0]
+    return gemm2d(H.reshape(R * I, Ap * Sp), Psi.reshape(S, Ap * Sp), transB=True).reshape(R, I, S)
+
+
+def env_update(side: str, env: torch.Tensor, G: torch.Tensor, bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """The interface of (bra, G, ket) moved over one site.  ``side == "left"``: env = Phi [R, A, R'] -> Phi' [S, A', S'] =
+    sum_{r, i} bra[r, i, s] H[r, i, a', s'] with H = env_half_apply(Phi, ket, G): a ttr_gemm with the first operand transposed.
+    ``side == "right"``: env = Psi [S, A', S'] -> Psi' [R, A, R']: the same kernel on the mirrored operands (rank-swapped views of
+    G and ket, read where they lie) and one transposed copy of the bra core."""
+    if side == "left":
+        H = env_half_apply(env, ket, G)
+        R, I, Ap, Sp = H.shape
+        return gemm2d(bra.reshape(R * I, -1), H.reshape(R * I, Ap * Sp), transA=True).reshape(-1, Ap, Sp)
+    if side != "right":
+        raise ValueError("env_update: side must be 'left' or 'right'")
+    braT = bra.permute(2, 1, 0).contiguous()                     # [s, i, r]
+    ketT = braT if ket is bra else ket.permute(2, 1, 0)
+    H = env_half_apply(env, ketT, G.permute(3, 1, 2, 0))         # [s, i, a, r']
+    S, I, A, Rp = H.shape
+    return gemm2d(braT.reshape(S * I, -1), H.reshape(S * I, A * Rp), transA=True).reshape(-1, A, Rp)

@@ -1022,3 +1022,33 @@ def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torc
         Gk = cores[k][:, digits[:, k]]                             # [R, P, O, S]
         Z = torch.einsum("pdr,rpos->pdos", Z, Gk).reshape(P, -1, Gk.shape[3])
     return Z.reshape(P, -1)
+
+
+# ---------------------------------------------------------------------------------------------- tt_solve (ttsolve.py)
+def gemm2d(A: torch.Tensor, B: torch.Tensor, transA: bool = False, transB: bool = False) -> torch.Tensor:
+    return (A.t() if transA else A) @ (B.t() if transB else B)
+
+
+def env_half_apply(Phi: torch.Tensor, X: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """Mirror of ttr_env_half_apply: Phi [R, A, R'], X [R', J, S'], G [A, I, J, A'] -> H [R, I, A', S'],
+    H[r, i, c, s] = sum_{a, j} G[a, i, j, c] sum_b Phi[r, a, b] X[b, j, s]."""
+    return torch.einsum("rab,bjs,aijc->rics", Phi, X, G).contiguous()
+
+
+env_half_apply_unfused = env_half_apply
+
+
+def local_matvec(Phi: torch.Tensor, G: torch.Tensor, Psi: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """y[r, i, s] = sum Phi[r, a, b] G[a, i, j, c] Psi[s, c, t] v[b, j, t]."""
+    return torch.einsum("rics,tcs->rit", env_half_apply(Phi, v, G), Psi)
+
+
+def env_update(side: str, env: torch.Tensor, G: torch.Tensor, bra: torch.Tensor, ket: torch.Tensor) -> torch.Tensor:
+    """The interface of (bra, G, ket) moved over one site: "left" Phi [R, A, R'] -> [S, A', S'], "right" Psi [S, A', S'] ->
+    [R, A, R'] (the mirrored operands)."""
+    if side == "left":
+        return torch.einsum("rit,rics->tcs", bra, env_half_apply(env, ket, G))
+    if side != "right":
+        raise ValueError("env_update: side must be 'left' or 'right'")
+    H = env_half_apply(env, ket.permute(2, 1, 0), G.permute(3, 1, 2, 0))   # [s, i, a, r']
+    return torch.einsum("ris,siab->rab", bra, H)
