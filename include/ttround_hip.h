@@ -389,7 +389,9 @@ int ttr_scale_cols(int dtype, int64_t rows, int64_t cols, int64_t batch,
                    void* out, int64_t ldo, int64_t stride_out, void* stream);
 /* x[b][:, j] <- 0 for j >= keep[b], in place (keep: device int32 [batch], e.g. ttr_eigh_trunc's info).  The device-side
  * form of `left = vectors[..., :rank]` (round.py:160-161) for a sweep that computes every bond at its rank cap and reads the
- * selected ranks back once, at the end (at most one host synchronisation per round_tt). */
+ * selected ranks back once, at the end (at most one host synchronisation per round_tt).
+ * keep[b] >= cols leaves item b untouched; keep[b] < 0 is clamped to 0 (the whole item is zeroed, nothing outside its
+ * rows x cols window is written). */
 int ttr_mask_cols(int dtype, int64_t rows, int64_t cols, int64_t batch, void* x, int64_t ldx, int64_t stride_x,
                   const int32_t* keep, void* stream);
 

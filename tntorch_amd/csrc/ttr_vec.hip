@@ -3,7 +3,7 @@
 //   ttr_norm            out[b] = ||x[b]||_2; one block per item  (torch.norm: tensor.py:2039-2051, round.py:80)
 //   ttr_scale_cols      out[b][:, j] = in[b][:, j] * s[b][j], or / s[b][j] (0 where |s| < tiny); grid (<= 2048 strides, items)
 //                       (left * sigma: round.py:169-172)
-//   ttr_mask_cols       x[b][:, j] = 0 for j >= keep[b]; grid (<= 1024 strides, items)
+//   ttr_mask_cols       x[b][:, j] = 0 for j >= keep[b] (keep[b] < 0 counts as 0); grid (<= 1024 strides, items)
 //                       (left = vectors[..., :rank] with the rank on the device: round.py:160-161)
 //   ttr_spectrum_flat   flat[b] = 1 when item b's spectrum lets it skip the second Gram pass; one thread per item
 //   ttr_carry_rows32    flag[b] = 1 when rows 32.. of the 64-row R[b] are negligible; one block per item
@@ -82,7 +82,7 @@ template <typename T>
 __global__ __launch_bounds__(kThreads) void mask_cols_kernel(int64_t rows, int64_t cols, T* __restrict__ x, int64_t ldx,
                                                              int64_t stride_x, const int32_t* __restrict__ keep) {
   const int64_t b = blockIdx.y;
-  const int64_t k = keep[b];
+  const int64_t k = keep[b] < 0 ? 0 : keep[b];  // (a negative count keeps nothing: j = k + idx % w must not start before the row)
   if (k >= cols) return;
   const int64_t w = cols - k, total = rows * w;
   for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kThreads) {
