@@ -168,6 +168,26 @@ def test_one_build_recipe():
     assert "-fno-slp-vectorize" in g.EXTRA_FLAGS["ttr_eigh.hip"]
 
 
+def test_every_included_header_is_a_build_dependency():
+    """Every quoted #include of the library's sources and headers names a file of the Makefile's HDR, which is also the list
+    ``build()`` checks for staleness: a header left out would mean silently stale objects."""
+    import __graft_entry__ as g
+
+    csrc = os.path.join(ROOT, "tntorch_amd", "csrc")
+    text = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    hdr = [os.path.normpath(os.path.join(csrc, h)) for h in re.search(r"^HDR\s*:=(.*)$", text, flags=re.M).group(1).split()]
+    assert g.HEADERS == hdr and len(set(hdr)) == len(hdr) and all(os.path.isfile(h) for h in hdr)
+    files = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
+    files += [os.path.join(csrc, "detail", f) for f in os.listdir(os.path.join(csrc, "detail")) if f.endswith(".h")]
+    seen = set()
+    for path in files:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
+            target = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+            assert target in hdr, f"{os.path.relpath(path, ROOT)} includes {inc}, which HDR does not list"
+            seen.add(target)
+    assert seen == set(hdr)   # and HDR lists nothing that no file includes
+
+
 def test_no_silent_fallback_for_device_tensors(monkeypatch):
     """A CUDA tensor must never be routed to the host mirror; missing library => RuntimeError."""
     import torch

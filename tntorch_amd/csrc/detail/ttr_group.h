@@ -11,6 +11,8 @@
 //                     needs when every sample brings `ra` rows, toff[I] = their total
 //   scatter_kernel    perm[off[v] + k] = the k-th sample (in no particular order) with index v   (cursor zeroed by the caller)
 // Every kernel but validate_kernel returns at entry when *flag is set.
+//   enqueue_group_sort  (host) the three launches above for one column
+//   group_of_tile       (device) the group a row tile of a consumer's step kernel belongs to
 #pragma once
 #include "../ttr_common.h"
 
@@ -125,6 +127,32 @@ __global__ void __launch_bounds__(kThreads) scatter_kernel(IdxCol c, int64_t P, 
     int64_t pos = lds ? (int64_t)base[v] + local : (int64_t)atomicAdd(&cursor[v], 1);
     perm[off[v] + pos] = q;
   }
+}
+
+// The group of row tile `mt` of the grouped row space (tiles of kGroupTileRows rows that never straddle two groups): the largest
+// v with toff[v] <= mt, found by thread 0 and handed round through *s_v, a word of the caller's LDS (a workgroup barrier: all
+// threads call this).  For mt < toff[I].  The tile's first row is row (mt - toff[v]) kGroupTileRows of the group's.
+__device__ __forceinline__ int64_t group_of_tile(const int64_t* toff, int64_t I, int64_t mt, int64_t* s_v) {
+  if (threadIdx.x == 0) {
+    int64_t hi = I - 1, lo = 0;   // (hi declared first: the other order swaps the operands of an addition in both callers)
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (toff[mid] <= mt) lo = mid; else hi = mid - 1;
+    }
+    *s_v = lo;
+  }
+  __syncthreads();
+  return *s_v;
+}
+
+// The counting sort of the P samples by column c, enqueued: perm lists the samples group by group, off / toff as scan_kernel
+// leaves them.  cnt and cursor ([I] each) are zeroed by the caller.
+inline void enqueue_group_sort(IdxCol c, int64_t P, int64_t I, int64_t ra, int32_t* cnt, int32_t* cursor, int64_t* off, int64_t* toff,
+                               int64_t* perm, const int32_t* flag, hipStream_t stream) {
+  const unsigned pb = (unsigned)((P + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(histogram_kernel, dim3(pb), dim3(kThreads), 0, stream, c, P, I, cnt, flag);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, I, ra, off, toff, flag);
+  hipLaunchKernelGGL(scatter_kernel, dim3(pb), dim3(kThreads), 0, stream, c, P, I, off, cursor, perm, flag);
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // What the translation units of libttround_hip.so share on the host and ttr_common.h does not hold: the prototypes of the
 // dispatchers the extern "C" wrappers call, the knob globals ttr_debug_set_knob writes, and the host helpers of the entries
-// (dtype checks and dispatch, stride and alignment tests, the argument checks of a core [R, I, C]).
+// (dtype checks and dispatch, stride and alignment tests, the argument checks of a core [R, I, C], the grid cap and the choice
+// of pack widths of the tile kernels).
 //
 // HOST-ONLY: no __global__ / __device__ code and no template a kernel instantiates.  Including this file therefore cannot
 // alter any kernel, which is why it may live outside the set of files bench.py hashes (csrc/*.h and the kernel sources:
@@ -11,6 +12,8 @@
 // checked against the declaration by the compiler (default arguments stand here, on the declaration, only), and a unit with
 // extern "C" entries takes its checks and its dtype dispatch from the helpers at the end instead of carrying copies.
 #pragma once
+#include <type_traits>
+
 #include "../ttr_common.h"
 
 namespace ttr {
@@ -145,6 +148,21 @@ inline bool contiguous(const int64_t* shape, const int64_t* strides, int nd) {
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
+
+// the grid of a kernel that walks `blocks` workgroups' worth of tiles or work items with a grid stride: that many, capped
+inline dim3 capped_grid(int64_t blocks) {
+  const int64_t cap = 1 << 20;
+  return dim3((unsigned)(blocks < cap ? blocks : cap));
+}
+
+// f(std::integral_constant<int, V>{}), V = the elements of a 16-byte pack of T where `wide`, else 1: picks the instance of a
+// kernel whose template argument is the width of its loads or stores (`decltype(v)::value` inside the generic lambda; nested
+// for two widths)
+template <typename T, typename F>
+void by_pack_width(bool wide, F&& f) {
+  if (wide) f(std::integral_constant<int, 16 / (int)sizeof(T)>{});
+  else f(std::integral_constant<int, 1>{});
+}
 
 // The checks of an entry `who` that reads one contiguous core X [R, I, C] and writes another buffer: dtype, sizes, pointers, the
 // strides of X, the index envelope.  `rest`: the entry's other pointers that must not be null, tested with X and `out`;

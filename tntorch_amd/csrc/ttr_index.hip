@@ -69,16 +69,7 @@ __global__ void __launch_bounds__(kThreads) step_kernel(const T* __restrict__ X,
     v = idx_value(c, p, I);
   } else {
     if (t >= toff[I]) return;
-    if (threadIdx.x == 0) {  // group of this tile: largest v with toff[v] <= t
-      int64_t lo = 0, hi = I - 1;
-      while (lo < hi) {
-        int64_t mid = (lo + hi + 1) >> 1;
-        if (toff[mid] <= t) lo = mid; else hi = mid - 1;
-      }
-      s_v = lo;
-    }
-    __syncthreads();
-    v = s_v;
+    v = group_of_tile(toff, I, t, &s_v);
     rbeg = off[v] * ra + (t - toff[v]) * kTileRows;
     rend = min(rbeg + kTileRows, (off[v] + cnt[v]) * ra);
   }
@@ -206,9 +197,7 @@ int gather_chain_impl(int64_t nmodes, int64_t batch, int64_t P, const int64_t* r
       } else {
         TTR_HIP_CHECK(hipMemsetAsync(cnt, 0, I * sizeof(int32_t), stream));
         TTR_HIP_CHECK(hipMemsetAsync(cursor, 0, I * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(histogram_kernel, dim3(pb), dim3(kThreads), 0, stream, c, P, I, cnt, flag);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, I, ra, off, toff, flag);
-        hipLaunchKernelGGL(scatter_kernel, dim3(pb), dim3(kThreads), 0, stream, c, P, I, off, cursor, perm, flag);
+        enqueue_group_sort(c, P, I, ra, cnt, cursor, off, toff, perm, flag, stream);
         tiles = (P * ra + kTileRows - 1) / kTileRows + I;  // upper bound: blocks past toff[I] return at once
       }
       dim3 grid((unsigned)tiles, (unsigned)((rn + kTileCols - 1) / kTileCols), (unsigned)batch);

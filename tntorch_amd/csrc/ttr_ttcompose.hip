@@ -31,8 +31,10 @@
 //
 // No workspace, no atomics, every element written exactly once.  j >= J is staged as zeros in both tiles and never read; a row
 // >= M or a column >= N of a short tile stages row 0 resp. column 0 of its operand (a valid address) and is never written.
-// Global offsets are 64-bit.
+// Global offsets are 64-bit.  The LDS strides, the live extents and the tested form of the multiply of one quad of j are
+// detail/ttr_mfma_tile.h's, shared with the other TT-matrix step kernels.
 #include "detail/ttr_internal.h"
+#include "detail/ttr_mfma_tile.h"
 
 namespace ttr {
 
@@ -41,8 +43,8 @@ namespace {
 constexpr int kTM = TTR_COMPOSE_TILE_M, kTN = TTR_COMPOSE_TILE_N, kTK = TTR_COMPOSE_TILE_K;
 static_assert(kTM == 64 && kTN == 64, "the loaders, the wave split and the store walk are written for 64 x 64 tiles");
 static_assert(kTK % 4 == 0 && kTK % (kThreads / 64) == 0, "a chunk of j is whole MFMA quads and whole loader passes");
-constexpr int kLd = kTM + 16;   // operand tiles, k-major: the 4 (fp64: 2) k of an operand read fall into disjoint banks
-constexpr int kLdc = kTN + 4;   // staged output tile: the 4 rows a lane group writes are 16 banks apart; rows stay 16-byte aligned
+constexpr int kLd = ld_kmajor(kTM);   // operand tiles, [k][m] and [k][n]
+constexpr int kLdc = ld_staged(kTN);  // staged output tile
 constexpr int kMagicShift = 20; // m = (local * ceil(2^20 / w)) >> 20 is local / w for local < 4096, w <= 64 (4095 * 63 < 2^20)
 
 template <typename T>
@@ -99,8 +101,7 @@ __global__ __launch_bounds__(kThreads) void core_compose_kernel(ComposeArgs<T> p
   const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);   // (uniform: kept in a scalar register)
   const int64_t mt = (int64_t)blockIdx.x / p.ntiles, nt = (int64_t)blockIdx.x - mt * p.ntiles;
   const int64_t m0 = mt * kTM, n0 = nt * kTN;
-  const int mrows = p.M - m0 < kTM ? (int)(p.M - m0) : kTM;   // live rows and columns of this tile, >= 1
-  const int ncols = p.N - n0 < kTN ? (int)(p.N - n0) : kTN;
+  const int mrows = live_extent(p.M, m0, kTM), ncols = live_extent(p.N, n0, kTN);   // live rows and columns of this tile, >= 1
   const int ntl = (ncols + 15) / 16;                          // live column tiles of 16
   const bool narrow = p.M <= 0xffffffffLL && p.N <= 0xffffffffLL;
   const int64_t RS = p.R2 * p.S2;
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void core_compose_kernel(ComposeArgs<T> p
   const T* pb = p.B + bbase + wave * bstep;
   const int64_t astep = (kThreads / 64) * p.R2, bstep4 = (kThreads / 64) * bstep;
   for (int64_t j0 = 0; j0 < p.J; j0 += kTK) {
-    const int klive = p.J - j0 < kTK ? (int)(p.J - j0) : kTK;
+    const int klive = live_extent(p.J, j0, kTK);
     const int quads = (klive + 3) / 4;   // the quads that are multiplied: only their rows are staged, the tail as zeros
     // `full` passes in which all four waves have a live j: straight-line code per count, all loads in flight together, then
     // the LDS stores.  A dead row or column (abase = 0, bbase = 0) reads A[0, 0, j, 0] resp. B[0, j, 0, 0] -- valid for a live
@@ -190,12 +191,7 @@ __global__ __launch_bounds__(kThreads) void core_compose_kernel(ComposeArgs<T> p
           for (int t = 0; t < kTN / 16; ++t) acc[t] = Mfma<T>::mma(a, b[t], acc[t]);
         }
       } else {
-        for (int q = 0; q < quads; ++q) {
-          const T a = a_row[q * 4 * kLd];
-#pragma unroll
-          for (int t = 0; t < kTN / 16; ++t)
-            if (t < ntl) acc[t] = Mfma<T>::mma(a, b_col[q * 4 * kLd + t * 16], acc[t]);
-        }
+        for (int q = 0; q < quads; ++q) mma_quad<T, kTN / 16, 16>(acc, a_row[q * 4 * kLd], b_col + q * 4 * kLd, ntl);
       }
     }
     __syncthreads();   // (the next chunk, or the staged output, overwrites As / Bs)

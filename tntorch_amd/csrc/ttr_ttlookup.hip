@@ -21,22 +21,21 @@
 //
 // X rows are loaded in 16-byte packs where R is a multiple of 16 bytes of elements and X is aligned (every row then starts on a
 // pack), the slice likewise where N and the strides of G are such multiples, (o, s) is one contiguous axis and G is aligned;
-// the arithmetic is the same.
+// the arithmetic is the same.  The LDS strides, stage_pack, the live extents and the multiply of one quad of k are
+// detail/ttr_mfma_tile.h's, shared with the other TT-matrix step kernels; the search for a row tile's group is ttr_group.h's.
 //
 // Index validation runs first (idx wraps negative values as in torch, xrow does not): a bad entry ORs *oob_flag with 1, and
 // every later kernel returns at entry when the word is set -- on entry or by this call.  The word is never cleared here: the
 // steps of a chain share it.
 #include "detail/ttr_internal.h"
 #include "detail/ttr_group.h"
+#include "detail/ttr_mfma_tile.h"
 
 namespace ttr {
 namespace {
 
 constexpr int kBM = kGroupTileRows, kBN = 64, kBK = 32;
-constexpr int kLdb = kBN + 16;           // slice tile row stride: the 4 (fp64: 2) k of an operand read fall into disjoint banks
-constexpr int64_t kMaxBlocks = 1 << 20;  // grid cap; the rest of the tiles is walked with a grid stride
-template <typename T>
-constexpr int lda_of() { return kBK + 16 / (int)sizeof(T); }  // X tile row stride (36 fp32 / 34 fp64): conflict-free operand reads
+constexpr int kLdb = ld_kmajor(kBN);  // slice tile, [k][n]
 
 template <typename T>
 struct LookupArgs {
@@ -57,18 +56,9 @@ struct LookupArgs {
   int64_t mtiles, ntiles;  // mtiles: an upper bound of toff[I]
 };
 
-template <typename T, int V>
-__device__ __forceinline__ void stage_pack(T* __restrict__ dst, const T* __restrict__ src, bool live) {
-  Pack<T, V> v;
-#pragma unroll
-  for (int j = 0; j < V; ++j) v.v[j] = T(0);
-  if (live) v = *reinterpret_cast<const Pack<T, V>*>(src);
-  *reinterpret_cast<Pack<T, V>*>(dst) = v;
-}
-
 template <typename T, int VA, int VB>
 __global__ __launch_bounds__(kThreads) void lookup_step_kernel(LookupArgs<T> p) {
-  constexpr int LDA = lda_of<T>();
+  constexpr int LDA = ld_rowmajor<T>(kBK);  // X tile, [m][k]
   __shared__ __attribute__((aligned(16))) T As[kBM * LDA];
   __shared__ __attribute__((aligned(16))) T Bs[kBK * kLdb];
   __shared__ int64_t xoff[kBM], yoff[kBM];
@@ -80,16 +70,7 @@ __global__ __launch_bounds__(kThreads) void lookup_step_kernel(LookupArgs<T> p) 
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t mt = tile / p.ntiles;
     const uint32_t n0 = (uint32_t)(tile - mt * p.ntiles) * kBN;
-    if (tid == 0) {  // group of this row tile: the largest v with toff[v] <= mt
-      int64_t lo = 0, hi = p.I - 1;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (p.toff[mid] <= mt) lo = mid; else hi = mid - 1;
-      }
-      s_v = lo;
-    }
-    __syncthreads();
-    const int64_t v = s_v;
+    const int64_t v = group_of_tile(p.toff, p.I, mt, &s_v);
     const int64_t rbeg = p.off[v] * p.D + (mt - p.toff[v]) * kBM;   // rows of the tile in grouped row space: (slot, dd)
     const int64_t rend = (p.off[v] + p.cnt[v]) * p.D;
     if (tid < kBM) {
@@ -105,8 +86,8 @@ __global__ __launch_bounds__(kThreads) void lookup_step_kernel(LookupArgs<T> p) 
       xoff[tid] = xo;
       yoff[tid] = yo;
     }
-    const int ncols = p.N - n0 < (uint32_t)kBN ? (int)(p.N - n0) : kBN;  // live columns of this tile, >= 1
-    const int ntl = (ncols + 15) / 16;                                   // live column tiles of 16
+    const int ncols = live_extent(p.N, n0, kBN);  // live columns of this tile, >= 1
+    const int ntl = (ncols + 15) / 16;            // live column tiles of 16
     // the slice column this thread stages (the same in every chunk of r)
     constexpr int per_row = kBN / VB;
     const int bn = (tid % per_row) * VB;
@@ -139,16 +120,10 @@ __global__ __launch_bounds__(kThreads) void lookup_step_kernel(LookupArgs<T> p) 
         stage_pack<T, VB>(Bs + kk * kLdb + bn, Gs + (int64_t)k * p.gr, bn_live && k < p.R);
       }
       __syncthreads();
-      const int klive = p.R - k0 < (uint32_t)kBK ? (int)(p.R - k0) : kBK;
-      const int quads = (klive + 3) / 4;
+      const int quads = (live_extent(p.R, k0, kBK) + 3) / 4;
       const T* a_row = As + (wave * 16 + (lane & 15)) * LDA + (lane >> 4);
       const T* b_col = Bs + (lane >> 4) * kLdb + (lane & 15);
-      for (int q = 0; q < quads; ++q) {
-        const T a = a_row[q * 4];
-#pragma unroll
-        for (int t = 0; t < kBN / 16; ++t)
-          if (t < ntl) acc[t] = Mfma<T>::mma(a, b_col[q * 4 * kLdb + t * 16], acc[t]);
-      }
+      for (int q = 0; q < quads; ++q) mma_quad<T, kBN / 16, 16>(acc, a_row[q * 4], b_col + q * 4 * kLdb, ntl);
       __syncthreads();  // (the next chunk, or the next tile, overwrites As / Bs)
     }
     // ---- store: lane holds column lane & 15 of rows Mfma<T>::row(lane, 0 .. 3) of each column tile
@@ -198,8 +173,7 @@ int lookup_impl(LookupArgs<T> p, int64_t rows_x, int32_t* flag, char* ws, const 
   p.flag = flag;
   p.mtiles = ceil_div(p.P * p.D, kBM) + p.I;  // every group rounds up by less than one tile
   p.ntiles = ceil_div((int64_t)p.N, kBN);
-  const int64_t tiles = p.mtiles * p.ntiles;
-  const dim3 grid((unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks));
+  const dim3 grid = capped_grid(p.mtiles * p.ntiles);
   const unsigned pb = (unsigned)ceil_div(p.P, kThreads);
   const bool va = p.R % VW == 0 && aligned16(p.X);
   const bool vb = p.S == p.N && p.N % VW == 0 && p.gr % VW == 0 && p.gi % VW == 0 && aligned16(p.G);
@@ -210,13 +184,12 @@ int lookup_impl(LookupArgs<T> p, int64_t rows_x, int32_t* flag, char* ws, const 
     hipLaunchKernelGGL(validate_kernel, dim3(pb), dim3(kThreads), 0, stream, cx, p.P, rows_x, flag, 0);  // no wrap: rows 0 .. rows_x-1
   }
   TTR_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * p.I * sizeof(int32_t), stream));
-  hipLaunchKernelGGL(histogram_kernel, dim3(pb), dim3(kThreads), 0, stream, p.idx, p.P, p.I, cnt, flag);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, p.I, p.D, off, toff, flag);
-  hipLaunchKernelGGL(scatter_kernel, dim3(pb), dim3(kThreads), 0, stream, p.idx, p.P, p.I, off, cursor, perm, flag);
-  if (va && vb) hipLaunchKernelGGL((lookup_step_kernel<T, VW, VW>), grid, dim3(kThreads), 0, stream, p);
-  else if (va) hipLaunchKernelGGL((lookup_step_kernel<T, VW, 1>), grid, dim3(kThreads), 0, stream, p);
-  else if (vb) hipLaunchKernelGGL((lookup_step_kernel<T, 1, VW>), grid, dim3(kThreads), 0, stream, p);
-  else hipLaunchKernelGGL((lookup_step_kernel<T, 1, 1>), grid, dim3(kThreads), 0, stream, p);
+  enqueue_group_sort(p.idx, p.P, p.I, p.D, cnt, cursor, off, toff, perm, flag, stream);
+  by_pack_width<T>(va, [&](auto VA) {
+    by_pack_width<T>(vb, [&](auto VB) {
+      hipLaunchKernelGGL((lookup_step_kernel<T, decltype(VA)::value, decltype(VB)::value>), grid, dim3(kThreads), 0, stream, p);
+    });
+  });
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }

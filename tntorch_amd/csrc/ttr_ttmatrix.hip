@@ -25,21 +25,21 @@
 //
 // No workspace, no atomics, no split of K across workgroups: every Y element is one chain of MFMA accumulations in increasing k,
 // its order fixed by the five extents and the dtype: the same call gives the same bits.
+// The LDS strides, stage_pack, the tile decode and the multiply of one quad of k are detail/ttr_mfma_tile.h's, shared with the
+// other TT-matrix step kernels.
 //
 // ttr_cpm_step is a streaming kernel on the vector ALUs: a thread owns a pack of 16 bytes of consecutive r of one (dd, o) where R
 // is a multiple of that and C, Y (and X, where it has a rank axis) are 16-byte aligned (else one element, same arithmetic) and
 // sums over i, increasing, with fma from 0, four i in flight.  Neighbouring threads are neighbouring packs of Y; X[i, dd, :] is re-read by the O threads of a dd from the cache.
 #include "detail/ttr_internal.h"
+#include "detail/ttr_mfma_tile.h"
 
 namespace ttr {
 
 namespace {
 
 constexpr int kBM = TTR_TTM_TILE_M, kBN = TTR_TTM_TILE_N, kBK = TTR_TTM_TILE_K;
-constexpr int kLdb = kBN + 16;                // B tile row stride: the 4 (fp64: 2) k of an operand read fall into disjoint banks
-constexpr int64_t kMaxBlocks = 1 << 20;       // grid cap; the rest of the tiles is walked with a grid stride
-template <typename T>
-constexpr int lda_of() { return kBK + 16 / (int)sizeof(T); }   // A tile row stride (36 fp32 / 34 fp64): conflict-free operand reads
+constexpr int kLdb = ld_kmajor(kBN);          // B tile, [k][n]
 
 template <typename T>
 struct TtmArgs {
@@ -52,21 +52,11 @@ struct TtmArgs {
   int64_t mtiles, ntiles;
 };
 
-// A pack of V consecutive elements from global memory to LDS (both aligned to the pack where V > 1), or V zeros
-template <typename T, int V>
-__device__ __forceinline__ void stage_pack(T* __restrict__ dst, const T* __restrict__ src, bool live) {
-  Pack<T, V> v;
-#pragma unroll
-  for (int j = 0; j < V; ++j) v.v[j] = T(0);
-  if (live) v = *reinterpret_cast<const Pack<T, V>*>(src);
-  *reinterpret_cast<Pack<T, V>*>(dst) = v;
-}
-
 // VA / VB: elements per load of the A / B tile (1, or 16 bytes' worth where R resp. N is a multiple of that and X resp. G is
 // 16-byte aligned: every pack then lies inside one run of r resp. one row of G, and inside the tile or outside it as a whole)
 template <typename T, bool P2, int VA, int VB>
 __global__ __launch_bounds__(kThreads) void ttm_step_kernel(TtmArgs<T> p) {
-  constexpr int LDA = lda_of<T>();
+  constexpr int LDA = ld_rowmajor<T>(kBK);    // A tile, [m][k]
   __shared__ __attribute__((aligned(16))) T As[kBM * LDA];
   __shared__ __attribute__((aligned(16))) T Bs[kBK * kLdb];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -75,11 +65,10 @@ __global__ __launch_bounds__(kThreads) void ttm_step_kernel(TtmArgs<T> p) {
   constexpr uint32_t BKu = kBK / VA;          // the A loader counts k in packs of VA: R, k0 and kBK are multiples of VA
   const uint32_t Ru = p.R / VA;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t mt = tile / p.ntiles;
-    const int64_t dd0 = mt * kBM;
-    const uint32_t n0 = (uint32_t)(tile - mt * p.ntiles) * kBN;
-    const int ncols = p.N - n0 < (uint32_t)kBN ? (int)(p.N - n0) : kBN;   // live columns of this tile, >= 1
-    const int ntl = (ncols + 15) / 16;                                  // live column tiles of 16
+    const TilePos<kBN> tp(tile, p.ntiles, p.N);
+    const int64_t dd0 = tp.mt * kBM;
+    const uint32_t n0 = tp.n0;
+    const int ncols = tp.ncols, ntl = tp.ntl;
     typename Mfma<T>::Acc acc[kBN / 16];
 #pragma unroll
     for (int t = 0; t < kBN / 16; ++t) acc[t] = Mfma<T>::zero();
@@ -113,16 +102,10 @@ __global__ __launch_bounds__(kThreads) void ttm_step_kernel(TtmArgs<T> p) {
         stage_pack<T, VB>(Bs + kk * kLdb + n, p.G + (((int64_t)r * p.I + i) * (int64_t)p.N + n0 + n), k < p.K && n < ncols);
       }
       __syncthreads();
-      const int klive = p.K - k0 < (uint32_t)kBK ? (int)(p.K - k0) : kBK;
-      const int quads = (klive + 3) / 4;
+      const int quads = (live_extent(p.K, k0, kBK) + 3) / 4;
       const T* a_row = As + (wave * 16 + (lane & 15)) * LDA + (lane >> 4);
       const T* b_col = Bs + (lane >> 4) * kLdb + (lane & 15);
-      for (int q = 0; q < quads; ++q) {
-        const T a = a_row[q * 4];
-#pragma unroll
-        for (int t = 0; t < kBN / 16; ++t)
-          if (t < ntl) acc[t] = Mfma<T>::mma(a, b_col[q * 4 * kLdb + t * 16], acc[t]);
-      }
+      for (int q = 0; q < quads; ++q) mma_quad<T, kBN / 16, 16>(acc, a_row[q * 4], b_col + q * 4 * kLdb, ntl);
       __syncthreads();   // (the next K tile, or the next tile of Y, overwrites As / Bs)
     }
     // ---- store: lane holds column lane & 15 of rows Mfma<T>::row(lane, 0 .. 3) of each column tile
@@ -146,20 +129,12 @@ inline int log2_exact(uint32_t v) {   // of a power of two
   return s;
 }
 
-template <typename T, bool P2, int VA>
-void ttm_launch(const TtmArgs<T>& p, bool vb, dim3 grid, hipStream_t stream) {
-  constexpr int VW = 16 / (int)sizeof(T);
-  if (vb) hipLaunchKernelGGL((ttm_step_kernel<T, P2, VA, VW>), grid, dim3(kThreads), 0, stream, p);
-  else hipLaunchKernelGGL((ttm_step_kernel<T, P2, VA, 1>), grid, dim3(kThreads), 0, stream, p);
-}
-
 template <typename T>
 int ttm_impl(TtmArgs<T> p, hipStream_t stream) {
   constexpr int VW = 16 / (int)sizeof(T);
   p.mtiles = ceil_div(p.D, kBM);
   p.ntiles = ceil_div((int64_t)p.N, kBN);
-  const int64_t tiles = p.mtiles * p.ntiles;
-  const dim3 grid((unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks));
+  const dim3 grid = capped_grid(p.mtiles * p.ntiles);
   const bool p2 = (p.R & (p.R - 1)) == 0;
   const bool va = p.R % VW == 0 && aligned16(p.X), vb = p.N % VW == 0 && aligned16(p.G);
   if (p2) {
@@ -168,10 +143,16 @@ int ttm_impl(TtmArgs<T> p, hipStream_t stream) {
     p.wsh = log2_exact(p.R < (uint32_t)kBK ? p.R : (uint32_t)kBK) - p.vsh;
   }
   ProfScope prof(TTR_PROF_GEMM, stream);
-  if (p2 && va) ttm_launch<T, true, VW>(p, vb, grid, stream);
-  else if (p2) ttm_launch<T, true, 1>(p, vb, grid, stream);
-  else if (va) ttm_launch<T, false, VW>(p, vb, grid, stream);
-  else ttm_launch<T, false, 1>(p, vb, grid, stream);
+  auto launch = [&](auto P2) {
+    by_pack_width<T>(va, [&](auto VA) {
+      by_pack_width<T>(vb, [&](auto VB) {
+        hipLaunchKernelGGL((ttm_step_kernel<T, decltype(P2)::value, decltype(VA)::value, decltype(VB)::value>), grid, dim3(kThreads),
+                           0, stream, p);
+      });
+    });
+  };
+  if (p2) launch(std::true_type{});
+  else launch(std::false_type{});
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }
@@ -241,8 +222,7 @@ __global__ __launch_bounds__(kThreads) void cpm_step_kernel(CpmArgs<T> p) {
 
 template <typename T, int P>
 void cpm_launch(const CpmArgs<T>& p, bool xr, hipStream_t stream) {
-  const int64_t blocks = ceil_div(p.D * p.O * (p.R / P), kThreads);
-  const dim3 grid((unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks));
+  const dim3 grid = capped_grid(ceil_div(p.D * p.O * (p.R / P), kThreads));
   if (xr) hipLaunchKernelGGL((cpm_step_kernel<T, P, true>), grid, dim3(kThreads), 0, stream, p);
   else hipLaunchKernelGGL((cpm_step_kernel<T, P, false>), grid, dim3(kThreads), 0, stream, p);
 }

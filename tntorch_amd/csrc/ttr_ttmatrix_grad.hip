@@ -32,29 +32,20 @@
 //
 // In LDS, rows >= D, columns past the output and k past K are zeros; they are never read from or written to global memory, and
 // column tiles of 16 past N and quads of k past K are not multiplied.
+// The LDS strides, stage_pack, ttr_ttm_grad_input's tile decode and the live k of a K tile are detail/ttr_mfma_tile.h's, shared
+// with the other TT-matrix step kernels.
 #include "detail/ttr_internal.h"
+#include "detail/ttr_mfma_tile.h"
 
 namespace ttr {
 
 namespace {
 
 constexpr int kBM = 64, kBN = 64, kBK = 32;
-constexpr int kLdk = kBN + 16;                // row stride of a tile stored [k][m or n]: the 4 (fp64: 2) k of an operand read fall into disjoint banks
-constexpr int kLdc = kBN + 4;                 // row stride of the staged output tile (16-byte aligned rows; rows 4 apart in disjoint banks)
-constexpr int64_t kMaxBlocks = 1 << 20;       // grid cap; the rest of the work items is walked with a grid stride
+constexpr int kLdk = ld_kmajor(kBN);          // a tile stored [k][m or n]
+constexpr int kLdc = ld_staged(kBN);          // the staged output tile
 constexpr int64_t kTargetGroups = 1024;       // slab rule: workgroups a long D is spread over
 constexpr int64_t kMinSlab = 256;             // slab rule: rows below which D is never cut
-template <typename T>
-constexpr int ldr_of() { return kBK + 16 / (int)sizeof(T); }   // row stride of a tile stored [m or n][k] (36 fp32 / 34 fp64), as ttr_ttm_step's A tile
-
-template <typename T, int V>
-__device__ __forceinline__ void stage_pack(T* __restrict__ dst, const T* __restrict__ src, bool live) {
-  Pack<T, V> v;
-#pragma unroll
-  for (int j = 0; j < V; ++j) v.v[j] = T(0);
-  if (live) v = *reinterpret_cast<const Pack<T, V>*>(src);
-  *reinterpret_cast<Pack<T, V>*>(dst) = v;
-}
 
 // ------------------------------------------------------------------ ttr_ttm_grad_input
 template <typename T>
@@ -71,7 +62,7 @@ struct GradInputArgs {
 // aligned); VS: elements per store (likewise, R and dX)
 template <typename T, int VL, int VS>
 __global__ __launch_bounds__(kThreads) void ttm_grad_input_kernel(GradInputArgs<T> p) {
-  constexpr int LDR = ldr_of<T>();
+  constexpr int LDR = ld_rowmajor<T>(kBK);    // a tile stored [m or n][k], as ttr_ttm_step's A tile
   constexpr int kOperands = 2 * kBM * LDR, kStaged = kBM * kLdc;
   __shared__ __attribute__((aligned(16))) T smem[kOperands > kStaged ? kOperands : kStaged];
   __shared__ int64_t Goff[kBN];               // element offset of the row of G behind column n0 + c of the tile, -1 past N
@@ -84,11 +75,10 @@ __global__ __launch_bounds__(kThreads) void ttm_grad_input_kernel(GradInputArgs<
   constexpr uint32_t BNu = kBN / VS;          // the store counts columns in packs of VS: R, n0 and kBN are multiples of VS
   const uint32_t Ru = p.R / VS;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t mt = tile / p.ntiles;
-    const int64_t dd0 = mt * kBM;
-    const uint32_t n0 = (uint32_t)(tile - mt * p.ntiles) * kBN;
-    const int ncols = p.N - n0 < (uint32_t)kBN ? (int)(p.N - n0) : kBN;   // live columns of this tile, >= 1
-    const int ntl = (ncols + 15) / 16;                                  // live column tiles of 16
+    const TilePos<kBN> tp(tile, p.ntiles, p.N);
+    const int64_t dd0 = tp.mt * kBM;
+    const uint32_t n0 = tp.n0;
+    const int ncols = tp.ncols, ntl = tp.ntl;
     if (tid < kBN) {
       const uint32_t n = n0 + tid, i = n / p.R, r = n - i * p.R;
       Goff[tid] = tid < ncols ? ((int64_t)r * p.I + i) * (int64_t)p.K : -1;
@@ -109,8 +99,7 @@ __global__ __launch_bounds__(kThreads) void ttm_grad_input_kernel(GradInputArgs<
         stage_pack<T, VL>(Bs + row * LDR + kk, p.G + (go + k0 + kk), klive && go >= 0);
       }
       __syncthreads();
-      const int klive = p.K - k0 < (uint32_t)kBK ? (int)(p.K - k0) : kBK;
-      const int quads = (klive + 3) / 4;
+      const int quads = (live_extent(p.K, k0, kBK) + 3) / 4;
       const T* a_row = As + (wave * 16 + (lane & 15)) * LDR + (lane >> 4);
       const T* b_row = Bs + (lane & 15) * LDR + (lane >> 4);
       for (int q = 0; q < quads; ++q) {
@@ -154,14 +143,14 @@ int grad_input_impl(GradInputArgs<T> p, hipStream_t stream) {
   constexpr int VW = 16 / (int)sizeof(T);
   p.mtiles = ceil_div(p.D, kBM);
   p.ntiles = ceil_div((int64_t)p.N, kBN);
-  const int64_t tiles = p.mtiles * p.ntiles;
-  const dim3 grid((unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks));
+  const dim3 grid = capped_grid(p.mtiles * p.ntiles);
   const bool vl = p.K % VW == 0 && aligned16(p.dY) && aligned16(p.G), vs = p.R % VW == 0 && aligned16(p.dX);
   ProfScope prof(TTR_PROF_GEMM, stream);
-  if (vl && vs) hipLaunchKernelGGL((ttm_grad_input_kernel<T, VW, VW>), grid, dim3(kThreads), 0, stream, p);
-  else if (vl) hipLaunchKernelGGL((ttm_grad_input_kernel<T, VW, 1>), grid, dim3(kThreads), 0, stream, p);
-  else if (vs) hipLaunchKernelGGL((ttm_grad_input_kernel<T, 1, VW>), grid, dim3(kThreads), 0, stream, p);
-  else hipLaunchKernelGGL((ttm_grad_input_kernel<T, 1, 1>), grid, dim3(kThreads), 0, stream, p);
+  by_pack_width<T>(vl, [&](auto VL) {
+    by_pack_width<T>(vs, [&](auto VS) {
+      hipLaunchKernelGGL((ttm_grad_input_kernel<T, decltype(VL)::value, decltype(VS)::value>), grid, dim3(kThreads), 0, stream, p);
+    });
+  });
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }
@@ -254,8 +243,7 @@ __global__ __launch_bounds__(kThreads) void ttm_grad_core_kernel(GradCoreArgs<T>
       lds_barrier();
       if (k0 + kBK < kend) fetch(k0 + kBK);
       if (wave_live) {
-        const int klive = kend - k0 < (int64_t)kBK ? (int)(kend - k0) : kBK;
-        const int quads = (klive + 3) / 4;
+        const int quads = (live_extent(kend, k0, kBK) + 3) / 4;
         const T* a_col = As + (lane >> 4) * kLdk + wave * 16 + (lane & 15);
         const T* b_col = Bs + (lane >> 4) * kLdk + (lane & 15);
         for (int q = 0; q < quads; ++q) {
@@ -337,18 +325,16 @@ int grad_core_impl(GradCoreArgs<T> p, hipStream_t stream) {
   constexpr int VW = 16 / (int)sizeof(T);
   p.mtiles = ceil_div((int64_t)p.M, kBM);
   p.ntiles = ceil_div((int64_t)p.N, kBN);
-  const int64_t items = p.mtiles * p.ntiles * p.nslab;
-  const dim3 grid((unsigned)(items < kMaxBlocks ? items : kMaxBlocks));
+  const dim3 grid = capped_grid(p.mtiles * p.ntiles * p.nslab);
   const bool va = p.R % VW == 0 && aligned16(p.X), vb = p.N % VW == 0 && aligned16(p.dY);
   ProfScope prof(TTR_PROF_GEMM, stream);
-  if (va && vb) hipLaunchKernelGGL((ttm_grad_core_kernel<T, VW, VW>), grid, dim3(kThreads), 0, stream, p);
-  else if (va) hipLaunchKernelGGL((ttm_grad_core_kernel<T, VW, 1>), grid, dim3(kThreads), 0, stream, p);
-  else if (vb) hipLaunchKernelGGL((ttm_grad_core_kernel<T, 1, VW>), grid, dim3(kThreads), 0, stream, p);
-  else hipLaunchKernelGGL((ttm_grad_core_kernel<T, 1, 1>), grid, dim3(kThreads), 0, stream, p);
-  if (p.nslab > 1) {
-    const int64_t blocks = ceil_div((int64_t)p.M * p.N, kRedCols);
-    hipLaunchKernelGGL(ttm_grad_core_reduce<T>, dim3((unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks)), dim3(kThreads), 0, stream, p);
-  }
+  by_pack_width<T>(va, [&](auto VA) {
+    by_pack_width<T>(vb, [&](auto VB) {
+      hipLaunchKernelGGL((ttm_grad_core_kernel<T, decltype(VA)::value, decltype(VB)::value>), grid, dim3(kThreads), 0, stream, p);
+    });
+  });
+  if (p.nslab > 1)
+    hipLaunchKernelGGL(ttm_grad_core_reduce<T>, capped_grid(ceil_div((int64_t)p.M * p.N, kRedCols)), dim3(kThreads), 0, stream, p);
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;
 }
