@@ -674,6 +674,12 @@ int ttr_debug_set_qr_stamps(void* device_buffer);
  *                      waves per SIMD, no scratch (1: 208 VGPRs, two waves) -- same results bit for bit; 3 = the 128-register
  *                      cap, which is that same build. */
 #define TTR_KNOB_EIGH_SMALL 8
+/*   TTR_KNOB_SWEEP_LEAN  1 (default) = fp32 launches of ttr_rowgram and ttr_project (kept rank <= 32) on 64-row matrices with a
+ *                      `rows32` pointer and >= 256 items run twice: a lean build of the kernel for the flagged items (rows 0 .. 31
+ *                      only: 3 Gram tiles with three slabs requested ahead / 8 K steps with the U fragments in registers; 8
+ *                      workgroups per CU instead of 4) and the generic build for the rest, each returning at once for the other's
+ *                      items -- same results bit for bit; 0 = the generic build alone (A/B). */
+#define TTR_KNOB_SWEEP_LEAN 19
 int ttr_debug_set_knob(int knob, int value);
 int ttr_prof_enable(int on);   /* 0 = off, 1 = per-kind device times, 2 = times + executed-work census (ttr_prof_collect_work) */
 /* Synchronises the recorded events; fills total milliseconds and launch counts per kind; resets. */

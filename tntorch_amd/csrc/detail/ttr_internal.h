@@ -115,6 +115,7 @@ extern int g_qr_pack_pre;
 extern int g_qr_l1_idle;
 extern int g_eigh_big_occ;
 extern int g_sweep_stagger;
+extern int g_sweep_lean;
 extern int g_rank_noise_c;
 extern int g_jacobi_live_wave;
 extern int g_eigh_small;

@@ -569,6 +569,10 @@ int ttr_debug_set_knob(int knob, int value) {
       TTR_REQUIRE(value >= 0 && value <= 2, TTR_E_INVALID, "ttr_debug_set_knob: stagger mode %d outside [0, 2]", value);
       g_sweep_stagger = value;
       return TTR_OK;
+    case TTR_KNOB_SWEEP_LEAN:
+      TTR_REQUIRE(value >= 0 && value <= 1, TTR_E_INVALID, "ttr_debug_set_knob: lean sweep switch %d outside [0, 1]", value);
+      g_sweep_lean = value;
+      return TTR_OK;
     case TTR_KNOB_EIGH_BIG_OCC:
       TTR_REQUIRE(value == 0 || value == 2 || value == 3, TTR_E_INVALID, "ttr_debug_set_knob: eigensolver occupancy %d not in {0, 2, 3}", value);
       g_eigh_big_occ = value;

@@ -214,8 +214,12 @@ constexpr int V1LD = 82;            // V1 as [k][m]: A-operand reads (16 k x 2 m
 constexpr int UBLK = 16 * V1LD;     // 1312 >= 16 * KLD
 __device__ __forceinline__ int urow(int k) { return (k >> 4) * UBLK + (k & 15) * KLD; }
 
-template <typename T>
+// REST: the second launch of a two-instance projection (project_typed) -- the items project_rows32_kernel has served return at once
+template <typename T, bool REST = false>
 __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_kernel(SweepArgs<T> p) {
+  if constexpr (REST) {
+    if (p.rows32[blockIdx.y] != 0) return;  // (block-uniform)
+  }
   using M = Mfma<T>;
   using Acc = typename M::Acc;
   // V2[:, :ro] as [m][i], zero padded (prologue only: leading dimension 72 instead of the conflict-free 80 -- with it the three
@@ -381,6 +385,269 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_ke
   }
   (void)al4;
 }
+
+// ---------------------------------------------------------------- lean builds for `rows32` items (fp32 launches, R = 64)
+// The carry of a packed bond has exactly zero rows 32..: on the metric EVERY item of the six large bonds.  The generic kernels
+// above skip the zero rows' loads and products, but they are built for 64 rows: 128 registers and 40 KB of LDS, four workgroups
+// per CU, one slab (rowgram) or one step (project) of 2 - 4 KB in flight per wave.  These instances hold what a 32-row item
+// needs -- <= 64 registers and 12 KB of LDS, eight workgroups per CU -- and compute the same sums in the same order: their results
+// are the generic kernels' bit for bit.  Items without the flag return at once; the generic instance serves them in a launch of
+// its own (gram_typed, project_typed).  Measured per large bond of the metric (4096 items, profiles/HISTORY.md): rowgram 260 ->
+// 244 us, project 460 -> 438 us on average, + 4.4 - 5.3 us for each returning launch.  The Gram kernel takes the same time at 3 .. 8 workgroups
+// per CU and with two or three slabs ahead: the ring and the unconditional loads are what it gains from, not the occupancy.
+constexpr int kLeanAhead = 3;  // rowgram: slabs requested ahead of the one being multiplied (a ring of kLeanAhead + 1)
+
+template <typename T>
+__global__ __launch_bounds__(kThreads, 8) void rowgram_rows32_kernel(SweepArgs<T> p) {
+  using M = Mfma<T>;
+  using Acc = typename M::Acc;
+  __shared__ __attribute__((aligned(16))) T red[4 * 3 * 256];  // per-wave partial tiles (0,0), (0,1), (1,1)
+  static_assert(std::is_same<T, float>::value, "slab loads and the write-out below assume the fp32 accumulator layout");
+  const int tid = threadIdx.x, lane = tid & 63, cl = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (the step counts below are scalars: plain branches)
+  const int64_t b = blockIdx.y;
+  if (p.rows32[b] == 0) return;  // (block-uniform)
+  const int split = blockIdx.x;
+  const T* __restrict__ Mp = p.M + b * p.strideM;
+  Acc G[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) G[i] = M::zero();
+  // chunks, steps and their order as in rotgram_kernel<T, true>: wave w takes chunks cb + w + 4 sq in ascending sq
+  const bool al = ((p.ldm & 3) == 0) && ((reinterpret_cast<uintptr_t>(Mp) & (4 * sizeof(T) - 1)) == 0);
+  int64_t cb, ce;
+  split_range((p.n + 15) / 16, p.nsplit, split, cb, ce);
+  auto gram_update = [&](const Acc (&mw)[2]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) G[0] = M::mma(mw[0][r], mw[0][r], G[0]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) G[1] = M::mma(mw[0][r], mw[1][r], G[1]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) G[2] = M::mma(mw[1][r], mw[1][r], G[2]);
+  };
+  const int64_t nsteps = ce > cb + wave ? (ce - cb - wave + 3) / 4 : 0;
+  const int64_t rot = (p.stagger >= 2 && nsteps > 1) ? (int64_t)(b % nsteps) : 0;
+  auto step_c = [&](int64_t sidx) { int64_t sq = sidx + rot; if (sq >= nsteps) sq -= nsteps; return cb + wave + 4 * sq; };
+  // Slab ring: step s lives in slot s mod NS; its loads are issued kLeanAhead steps early, into the slot the previous step has
+  // just left.  The loop has no stores and the loads return in order, so every step waits for its own slab only -- provided the
+  // compiler can count them: WIDE (aligned rows, whole chunks: the block's share ends inside n) issues every load
+  // unconditionally, and the steady state below tests no step index.
+  constexpr int NS = kLeanAhead + 1;
+  auto run = [&](auto WIDEC) {
+    constexpr bool WIDE = decltype(WIDEC)::value;
+    auto load_slab = [&](int64_t c, Acc (&mw)[2]) {
+      const int64_t col = c * 16 + 4 * g;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const T* src = Mp + (int64_t)(16 * t + cl) * p.ldm + col;
+        if constexpr (WIDE) {
+          mw[t] = *reinterpret_cast<const Acc*>(src);
+        } else {
+          const Pack<T, 4> x = load_pack<T, 4>(src, al, p.n - col);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) mw[t][r] = x.v[r];
+        }
+      }
+    };
+    Acc slab[NS][2];
+    int64_t s0 = 0;
+    if (nsteps >= NS + kLeanAhead) {  // steady state: NS steps per round, as long as each of them has a slab to request
+#pragma unroll
+      for (int d = 0; d < kLeanAhead; ++d) load_slab(step_c(d), slab[d]);
+      do {
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          load_slab(step_c(s0 + u + kLeanAhead), slab[(u + kLeanAhead) % NS]);
+          __builtin_amdgcn_sched_barrier(0);  // (the scheduler would gather the ring's loads at the end of the body, behind one wait for all)
+          gram_update(slab[u]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        s0 += NS;
+      } while (s0 + NS + kLeanAhead <= nsteps);
+    } else {
+#pragma unroll
+      for (int d = 0; d < kLeanAhead; ++d)
+        if (d < nsteps) load_slab(step_c(d), slab[d]);
+    }
+    for (; s0 < nsteps; s0 += NS) {
+#pragma unroll
+      for (int u = 0; u < NS; ++u) {
+        const int64_t sidx = s0 + u;
+        if (sidx < nsteps) {  // (wave-uniform)
+          if (sidx + kLeanAhead < nsteps) load_slab(step_c(sidx + kLeanAhead), slab[(u + kLeanAhead) % NS]);
+          gram_update(slab[u]);
+        }
+      }
+    }
+  };
+  if (al && ce * 16 <= p.n) run(std::true_type{});
+  else run(std::false_type{});
+  // reduce the four waves' partial tiles, (w0 + w1) + (w2 + w3) as in the generic kernel, and write the whole 64 x 64 partial:
+  // both triangles of the 32 x 32 block, zeros around it
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[(wave * 3 + i) * 256 + lane * 4 + r] = G[i][r];
+  __syncthreads();
+  T* __restrict__ Gout = p.G + ((int64_t)b * p.nsplit + split) * 64 * 64;
+  for (int idx = tid; idx < 64 * 64; idx += kThreads) {
+    const int row = idx >> 6, col = idx & 63;
+    T v = T(0);
+    if (row < 32 && col < 32) {
+      // tile (ti, tj), ti <= tj, holds element (i, j) in lane 16 (i / 4) + j, register i mod 4; the lower triangle mirrors (0, 1)
+      const bool low = row >= 16 && col < 16;
+      const int i = (low ? col : row) & 15, j = (low ? row : col) & 15;
+      const int tile = (row >> 4) + (col >> 4);
+      const int e = tile * 256 + ((i >> 2) * 16 + j) * 4 + (i & 3);
+      v = (red[e] + red[768 + e]) + (red[1536 + e] + red[2304 + e]);
+    }
+    Gout[idx] = v;
+  }
+}
+
+constexpr int ULD = 48;  // leading dimension of the lean projection's 32-column image [k][i]: the fragment reads of a wave (16 i x
+                         // 4 k: words 48 g + cl) hit 64 different banks
+
+template <typename T>
+__global__ __launch_bounds__(kThreads, 8) void project_rows32_kernel(SweepArgs<T> p) {
+  using M = Mfma<T>;
+  using Acc = typename M::Acc;
+  __shared__ __attribute__((aligned(16))) T Wl[64 * ULD];  // V2[:, :ro] as [m][i], zero padded to 32 columns; then U as [k][i]
+  __shared__ T isg[32];                                    // as in project_kernel
+  static_assert(std::is_same<T, float>::value, "the store addresses below assume the fp32 accumulator layout");
+  const int tid = threadIdx.x, lane = tid & 63, cl = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (a scalar: the step's range test below is a plain branch)
+  const int64_t b = blockIdx.y;
+  if (p.rows32[b] == 0) return;  // (block-uniform)
+  const int split = blockIdx.x;
+  const T* __restrict__ Mp = p.M + b * p.strideM;
+  const int ro = p.ro;           // <= 32, R = 64 (project_typed)
+  const int nt = (ro + 15) / 16;
+  const T* __restrict__ V2 = p.V2 + b * p.strideV2;
+  const T* __restrict__ sg = p.sigma ? p.sigma + b * p.stride_sigma : nullptr;
+  T* __restrict__ Lo = (p.left && split == 0) ? p.left + b * p.strideL : nullptr;
+  // ---- prologue: the sums of project_kernel's in the same order.  V1 is not staged: wave w reads ITS 16 rows straight from global
+  // memory as the A operand (lane (g, cl), K step ks <-> V1[16 w + cl][4 ks + g]), and U replaces V2 in the one image.
+  for (int idx = tid; idx < 64 * 32; idx += kThreads) {
+    const int m = idx >> 5, i = idx & 31;
+    Wl[m * ULD + i] = (i < ro) ? V2[(int64_t)m * p.ldv2 + i] : T(0);
+  }
+  if (tid < 32) {
+    T sc = T(1);
+    if (p.scale_right && sg && tid < ro) {
+      const T x = sg[tid];
+      sc = (fabs((double)x) < (double)Num<T>::tiny()) ? T(0) : T(1) / x;
+    }
+    isg[tid] = sc;
+  }
+  if (p.V1) {
+    const T* __restrict__ V1 = p.V1 + b * p.strideV1 + (int64_t)(16 * wave + cl) * p.ldv1 + g;
+    T a[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) a[ks] = V1[4 * ks];
+    __syncthreads();
+    Acc u0 = M::zero(), u1 = M::zero();
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+      u0 = M::mma(a[ks], Wl[(4 * ks + g) * ULD + cl], u0);
+      u1 = M::mma(a[ks], Wl[(4 * ks + g) * ULD + 16 + cl], u1);
+    }
+    __syncthreads();  // every wave has read V2: U takes its place
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      T* dst = Wl + (16 * wave + M::row(lane, r)) * ULD + cl;
+      dst[0] = u0[r];
+      dst[16] = u1[r];
+    }
+  }
+  __syncthreads();
+  if (Lo) {  // left = U diag(sigma): all 64 rows
+    for (int idx = tid; idx < 64 * ro; idx += kThreads) {
+      const int k = idx / ro, i = idx - k * ro;
+      const T u = Wl[k * ULD + i];
+      Lo[(int64_t)k * p.ldl + i] = (p.scale_right && sg) ? u * sg[i] : u;
+    }
+  }
+  // ---- main loop: project_kernel's with NK = 8 and SL = 2 (same steps, same stagger, same K order).  Rows 0 .. 31 of U are all
+  // it multiplies by: the wave's 16 fragments stay in registers.
+  T af[2][8];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) af[t][ks] = Wl[(4 * ks + g) * ULD + 16 * t + cl];
+  T* __restrict__ Ro = p.right + b * p.strideR;
+  const bool al = ((p.ldm & 1) == 0) && ((p.ldr & 1) == 0) && ((reinterpret_cast<uintptr_t>(Mp) & (2 * sizeof(T) - 1)) == 0) &&
+                  ((reinterpret_cast<uintptr_t>(Ro) & (2 * sizeof(T) - 1)) == 0);
+  int64_t cb, ce;
+  split_range((p.n + 31) / 32, p.nsplit, split, cb, ce);
+  const int64_t col_b = cb * 32, col_e = ce * 32 < p.n ? ce * 32 : p.n;
+  const int64_t nch = (col_e - col_b + 31) / 32;
+  const int64_t nsteps = nch > wave ? (nch - wave + 3) / 4 : 0;
+  const int64_t rot = (p.stagger && nsteps > 1) ? (int64_t)(b % nsteps) : 0;
+  // (addresses: the lane's part g ldm + col / 4 g ldr + col once per step, its column behind an empty asm so that the compiler adds
+  // the wave-uniform row offsets per access instead of keeping sixteen 64-bit row pointers -- they do not fit 64 registers)
+  const T* __restrict__ Mg = Mp + (int64_t)g * p.ldm;
+  T* __restrict__ Rg = Ro + (int64_t)M::row(lane, 0) * p.ldr;
+  // WHOLE: aligned rows and the wave's 32 columns all inside the share -- every access of the step is unconditional.  (With the
+  // guarded accesses of load_pack in the one path the compiler, short of registers, waits for each load before the next.)
+  typedef T VT __attribute__((ext_vector_type(2)));
+  auto step = [&](auto WHOLEC, const T* mk, T* rk, int64_t lim) {
+    constexpr bool WHOLE = decltype(WHOLEC)::value;
+    T bm[2][8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const T* src = mk + (int64_t)(4 * ks) * p.ldm;
+      if constexpr (WHOLE) {
+        const VT x = *reinterpret_cast<const VT*>(src);
+        bm[0][ks] = x[0];
+        bm[1][ks] = x[1];
+      } else {
+        const Pack<T, 2> x = load_pack<T, 2>(src, al, lim > 0 ? lim : 0);
+        bm[0][ks] = x.v[0];
+        bm[1][ks] = x.v[1];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      if (t < nt) {
+        Acc acc[2] = {M::zero(), M::zero()};
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+#pragma unroll
+          for (int u = 0; u < 2; ++u) acc[u] = M::mma(af[t][ks], bm[u][ks], acc[u]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * t + M::row(lane, r);
+          if (row < ro && (WHOLE || lim > 0)) {
+            const T sc = isg[row];
+            T* dst = rk + (int64_t)(16 * t + r) * p.ldr;  // (fp32 layout: M::row(lane, r) = M::row(lane, 0) + r -- a scalar offset)
+            if (WHOLE || (al && lim >= 2)) {
+              VT o;
+              o[0] = acc[0][r] * sc;
+              o[1] = acc[1][r] * sc;
+              *reinterpret_cast<VT*>(dst) = o;
+            } else {
+              dst[0] = acc[0][r] * sc;
+              if (lim > 1) dst[1] = acc[1][r] * sc;
+            }
+          }
+        }
+      }
+    }
+  };
+  for (int64_t sidx = 0; sidx < nsteps; ++sidx) {
+    int64_t sq = sidx + rot;
+    if (sq >= nsteps) sq -= nsteps;
+    const int64_t cw = col_b + (wave + 4 * sq) * 32;  // (wave-uniform) the step's first column
+    int64_t col = cw + 2 * cl;
+    asm volatile("" : "+v"(col));
+    const T* mk = Mg + col;
+    T* rk = Rg + col;
+    if (al && cw + 32 <= col_e) step(std::true_type{}, mk, rk, 2);
+    else step(std::false_type{}, mk, rk, col_e - col);  // (columns of the lane's pair inside the split's share)
+  }
+}
+
 
 // ================================================================ tall matrices (dense TT-SVD steps): M is rows x n, n <= 64
 // The first (largest) step of a dense right-to-left TT-SVD truncates a (prod I_1..I_{N-1}) x I_N unfolding: millions of
@@ -758,6 +1025,9 @@ int colproject_dispatch(int dtype, int64_t rows, int64_t n, int64_t ro, int64_t 
 }
 
 int g_sweep_stagger = 1;   // ttr_debug_set_knob(TTR_KNOB_SWEEP_STAGGER)
+int g_sweep_lean = 1;      // ttr_debug_set_knob(TTR_KNOB_SWEEP_LEAN)
+// launches of fewer items run the generic instance alone (latency-bound sizes: a second launch costs more than the build gains)
+constexpr int64_t kLeanMinItems = 256;
 
 static int pick_split(int64_t n, int64_t batch) {
   const int64_t chunks = (n + 31) / 32;        // (the projection walks 32 columns per step and wave)
@@ -801,6 +1071,14 @@ static int gram_typed(int64_t R, int64_t n, int64_t batch, const void* Mx, int64
     if (skip) q.skip = skip + b0;
     if (rows32) q.rows32 = rows32 + b0;
     const dim3 grid((unsigned)nsplit, (unsigned)nb);
+    if constexpr (std::is_same<T, float>::value) {
+      // two instances (TTR_KNOB_SWEEP_LEAN; the pattern of QrLevel::live_half): the lean build takes the `rows32` items, and the
+      // generic one sees their flags as its `skip` flags
+      if (g_sweep_lean && !V1 && !skip && rows32 && R == 64 && nb >= kLeanMinItems) {
+        hipLaunchKernelGGL(rowgram_rows32_kernel<T>, grid, dim3(kThreads), 0, stream, q);
+        q.skip = q.rows32;
+      }
+    }
     if (V1) hipLaunchKernelGGL((rotgram_kernel<T, false>), grid, dim3(kThreads), 0, stream, q);
     else hipLaunchKernelGGL((rotgram_kernel<T, true>), grid, dim3(kThreads), 0, stream, q);
   }
@@ -850,7 +1128,16 @@ static int project_typed(int64_t R, int64_t n, int64_t ro, int64_t batch, const 
     q.right = p.right + b0 * strideR;
     if (left) q.left = p.left + b0 * strideL;
     if (rows32) q.rows32 = rows32 + b0;
-    hipLaunchKernelGGL(project_kernel<T>, dim3((unsigned)p.nsplit, (unsigned)nb), dim3(kThreads), 0, stream, q);
+    const dim3 grid((unsigned)p.nsplit, (unsigned)nb);
+    bool two = false;
+    if constexpr (std::is_same<T, float>::value) {   // two instances, as in gram_typed
+      two = g_sweep_lean && rows32 && R == 64 && ro <= 32 && nb >= kLeanMinItems;
+      if (two) {
+        hipLaunchKernelGGL(project_rows32_kernel<T>, grid, dim3(kThreads), 0, stream, q);
+        hipLaunchKernelGGL((project_kernel<T, true>), grid, dim3(kThreads), 0, stream, q);
+      }
+    }
+    if (!two) hipLaunchKernelGGL((project_kernel<T, false>), grid, dim3(kThreads), 0, stream, q);
   }
   TTR_HIP_CHECK(hipGetLastError());
   return TTR_OK;

@@ -15,7 +15,8 @@ CSRC = os.path.join(ROOT, "tntorch_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HOT = ("qr_factor_kernel<float, 4, true, 8, true, 8>", "qr_factor_kernel<float, 4, false, 8, true, 8>",
        "qr_factor_kernel<float, 4, false, 8, true, 6>", "qr_factor_kernel<float, 4, false, 8, true, 4>", "qr_apply_kernel<float, 4, 2, 8>",
-       "project_kernel<float>", "rotgram_kernel<float, true>", "rotgram_kernel<float, false>", "eigh_tridiag_kernel<float, true, 32, 3>",
+       "project_kernel<float, false>", "project_rows32_kernel<float>", "rotgram_kernel<float, true>", "rowgram_rows32_kernel<float>",
+       "rotgram_kernel<float, false>", "eigh_tridiag_kernel<float, true, 32, 3>",
        "eigh_tridiag_kernel<float, true, 64, 0>", "eigh_jacobi_kernel<float, true, 256>", "colgram_kernel<float, false>",
        "colproject_kernel<float, false>", "gemm_big_kernel<float>", "pack_flags_kernel<float>", "qr_factor_kernel<double, 4, true, 8, true, 8>",
        "qr_apply_kernel<double, 4, 2, 8>")

@@ -32,7 +32,9 @@ def kind_of(name):
         return "krp_contract"
     if "rotgram_kernel" in name:
         return "rowgram" if re.search(r"rotgram_kernel<\w+, true>", name) else "rotgram"
-    if "project_kernel" in name and "colproject" not in name:
+    if "rowgram_rows32_kernel" in name:
+        return "rowgram"
+    if ("project_kernel" in name or "project_rows32_kernel" in name) and "colproject" not in name:
         return "project"
     if "eigh_" in name:
         return "eigh"
