@@ -56,7 +56,8 @@ extern "C" {
    round 5: 10 = ttr_round_tt, the whole sweep behind one call, + TTR_KNOB_RANK_NOISE_FLOOR; 11 = ttr_qr_factor_expo / ttr_qr_factor_pushed_expo; 12 = ttr_gather_chain; 13 = ttr_maxvol, ttr_gather_step; 14 = ttr_als_normal, ttr_spd_solve, ttr_pinv_finish; 15 = ttr_sparse_keys, ttr_sparse_levels, ttr_sparse_group, ttr_sparse_gram, ttr_sparse_project; 16 = ttr_core_matvec, ttr_hsum_step; 17 = ttr_mode_diff, ttr_laplace_core; ttr_core_convolve, ttr_accept_count / ttr_accept_expand, ttr_mode_scan / ttr_mode_reduce, ttr_pce_design / ttr_pce_predict, ttr_mode_sandwich, ttr_sample_max_rank / ttr_sample_step and ttr_ttm_step / ttr_cpm_step were ADDED under 17: no existing signature changed, and a library without the
    symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
    ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
-   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose, and ttr_env_half_apply.  ttr_version() returns the value the library was built with; the Python
+   ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose, and ttr_env_half_apply, and ttr_ritz_parts, ttr_ritz_workspace_bytes, ttr_ritz_gram and
+   ttr_ritz_update.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1293,6 +1294,63 @@ int ttr_core_compose(int dtype, int64_t R1, int64_t P, int64_t J, int64_t R2, in
 #define TTR_ENV_TILE_K 16
 int ttr_env_half_apply(int dtype, int64_t R, int64_t A, int64_t Rp, int64_t J, int64_t Sp, int64_t I, int64_t Ap, const void* Phi,
                        const void* X, const int64_t* x_strides, const void* G, const int64_t* g_strides, void* H, void* stream);
+
+/*
+ * One Rayleigh-Ritz step of a three-vector LOBPCG in two launches, the local eigensolver of the ALS eigenvalue solver (added under
+ * ABI 17; tteigs.py `tt_eigsh`).  The state of a local problem B v = theta v is six contiguous vectors of n
+ * elements in the dtype: X, AX = B X, W (the residual AX - theta X), AW = B W (the caller's matvec), P and AP (the previous
+ * direction).  None of the six may overlap another.
+ *
+ * ttr_ritz_parts / ttr_ritz_workspace_bytes: the number of workgroups of the Gram launch, 1 + (ceil(n / V) - 1) / 1024 capped at
+ * TTR_RITZ_MAX_PARTS with V = 16 bytes / element size, and the bytes of `part`, 12 doubles per workgroup.  Both are functions of
+ * n and the dtype alone, so the association of every sum is fixed by n and the dtype.  TTR_E_INVALID (negative) for a bad dtype
+ * or n < 1.
+ *
+ * ttr_ritz_gram: part[g][0..12) = workgroup g's share of S = V^T V and T = V^T A V for V = [X W P], upper triangles:
+ *     S_xx S_xw S_xp S_ww S_wp S_pp   T_xx = X.AX  T_xw = X.AW  T_xp = X.AP  T_ww = W.AW  T_wp = W.AP  T_pp = P.AP
+ * One pass over the vectors; products and sums in double (one fma per product); 16-byte packs where every pointer is 16-byte
+ * aligned, element loads with the same arithmetic otherwise and for the last pack of an n that is no multiple of V.  Pack p belongs
+ * to thread p % 256 of workgroup (p / 256) % parts, which adds its packs in increasing p; lanes meet in the library's wave sum, the
+ * four waves in increasing order.  The same call gives the same bits, aligned or not.  No atomics.
+ * mode TTR_RITZ_INIT reads only X and AX and fills S_xx and T_xx (the other ten are zeros; W .. AP may be NULL); in
+ * TTR_RITZ_STEP P and AP may both be NULL: zeros, not read.
+ *
+ * ttr_ritz_update: every workgroup adds the rows of `part` in increasing g (the previous launch's reduction, finished in this
+ * one's prologue), one thread solves the pencil in double, and the workgroup updates its slice of the vectors in place, every
+ * element read and written by the same thread.
+ *   TTR_RITZ_INIT   X <- X / ||X||, AX <- AX / ||X||, theta' = T_xx / S_xx, W <- AX - theta' X, P <- AP <- 0 (AW is not read;
+ *                   P and AP may both be NULL)
+ *   TTR_RITZ_STEP   res = sqrt(S_ww / (S_ww + theta^2 S_xx)) with theta = T_xx / S_xx, the incoming ||W|| / ||AX|| (0 for
+ *                   S_ww = 0).  res <= rel: the step is FROZEN and writes no vector.  Otherwise the extreme Ritz pair (`which`:
+ *                   TTR_RITZ_SA the smallest, TTR_RITZ_LA the largest) of (T, S): S is scaled to unit diagonal, a zero diagonal
+ *                   dropping its direction; the eigendirections of the scaled S below TTR_RITZ_DROP eps (eps of the dtype) of
+ *                   its largest eigenvalue are dropped; the whitened problem is solved (cyclic Jacobi); the coefficients c are
+ *                   scaled to c^T S c = 1 with c0 >= 0 and theta' = c^T T c.  Then
+ *                       Pn = c1 W + c2 P, APn = c1 AW + c2 AP, X <- c0 X + Pn, AX <- c0 AX + APn, P <- Pn, AP <- APn,
+ *                       W <- AX - theta' X   (of the rounded new X and AX)
+ *                   evaluated in double and rounded once.  P and AP both NULL: zeros, neither read nor written.
+ * Workgroup 0 overwrites state[0..8) = theta', res, frozen, flags (1: a non-finite sum, 2: S_xx == 0; a flagged step writes no
+ * vector and has theta' = 0), c0, c1, c2, the number of directions kept (0 for a frozen or flagged step, whose c is (1, 0, 0)),
+ * and accumulates sweep[0..4): [0] = max([0], res) when `first` is set, [1] += (flags != 0), [2] = theta', [3] |= flags (as an
+ * integer).  Nothing is read back.
+ *
+ * Before any launch: TTR_E_INVALID for a bad dtype, mode or `which`, n < 1, rel < 0, a null pointer (or only one of P and AP);
+ * TTR_E_WORKSPACE for workspace_bytes below ttr_ritz_workspace_bytes; TTR_E_UNSUPPORTED for n of 2^57 or more.
+ * `part` given to ttr_ritz_update must hold the ttr_ritz_parts(dtype, n) rows ttr_ritz_gram wrote for the same n and dtype.
+ * Profiling kind: TTR_PROF_MISC.
+ */
+#define TTR_RITZ_INIT 0
+#define TTR_RITZ_STEP 1
+#define TTR_RITZ_SA 0
+#define TTR_RITZ_LA 1
+#define TTR_RITZ_MAX_PARTS 256
+#define TTR_RITZ_DROP 64
+int ttr_ritz_parts(int dtype, int64_t n);
+int64_t ttr_ritz_workspace_bytes(int dtype, int64_t n);
+int ttr_ritz_gram(int dtype, int mode, int64_t n, const void* X, const void* AX, const void* W, const void* AW, const void* P,
+                  const void* AP, double* part, int64_t workspace_bytes, void* stream);
+int ttr_ritz_update(int dtype, int mode, int which, int first, int64_t n, double rel, const double* part, void* X, void* AX, void* W,
+                    const void* AW, void* P, void* AP, double* state, double* sweep, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1805,3 +1805,64 @@ def env_half_apply(Phi: torch.Tensor, X: torch.Tensor, G: torch.Tensor, out: Opt
     _call("ttr_env_half_apply", dt, R, A, Rp, J, Sp, I, Ap, Phi.data_ptr(), X.data_ptr(), _i64(X.stride()), G.data_ptr(),
           _i64(G.stride()), out.data_ptr())
     return out.view(shape)
+
+
+def ritz_parts(dt: torch.dtype, n: int) -> int:
+    """ttr_ritz_parts: the workgroups of the Gram launch for vectors of n elements, a function of n and the dtype alone."""
+    parts = int(lib().ttr_ritz_parts(dtype_code(dt), int(n)))
+    if parts < 0:
+        _check(parts, "ttr_ritz_parts")
+    return parts
+
+
+def ritz_workspace_bytes(dt: torch.dtype, n: int) -> int:
+    """ttr_ritz_workspace_bytes: the bytes of ``part``, 12 doubles per workgroup of the Gram launch."""
+    wsb = int(lib().ttr_ritz_workspace_bytes(dtype_code(dt), int(n)))
+    if wsb < 0:
+        _check(wsb, "ttr_ritz_workspace_bytes")
+    return wsb
+
+
+def _ritz_vectors(who: str, X: torch.Tensor, others) -> int:
+    if not (X.is_cuda and X.dim() == 1 and X.is_contiguous()):
+        raise ValueError("{}: X must be a contiguous device vector".format(who))
+    for v in others:
+        if v is not None and not (v.shape == X.shape and v.dtype == X.dtype and v.device == X.device and v.is_contiguous()):
+            raise ValueError("{}: the vectors must be contiguous, of X's length and dtype and on its device".format(who))
+    return int(X.numel())
+
+
+@_on_device
+def ritz_gram(mode: int, X: torch.Tensor, AX: torch.Tensor, W: Optional[torch.Tensor] = None, AW: Optional[torch.Tensor] = None,
+              P: Optional[torch.Tensor] = None, AP: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ritz_gram: the fp64 partial sums [parts, 12] of S = V^T V and T = V^T A V, V = [X W P], for contiguous device vectors of
+    one length and dtype (a view that starts off a 16-byte boundary takes the element loads, same bits).  ``mode`` is RITZ_INIT
+    (X and AX only) or RITZ_STEP (P = AP = None: zeros, not read).  ``part``: a contiguous fp64 tensor that receives them."""
+    n = _ritz_vectors("ritz_gram", X, (AX, W, AW, P, AP))
+    dt = dtype_code(X.dtype)
+    if part is None:
+        part = torch.empty((ritz_parts(X.dtype, max(n, 1)), 12), dtype=torch.float64, device=X.device)
+    if not (part.dtype == torch.float64 and part.is_contiguous() and part.device == X.device):
+        raise ValueError("ritz_gram: part must be a contiguous fp64 tensor on the vectors' device")
+    _call("ttr_ritz_gram", dt, int(mode), n, X.data_ptr(), AX.data_ptr(), _ptr(W), _ptr(AW), _ptr(P), _ptr(AP), part.data_ptr(),
+          int(part.numel()) * 8)
+    return part
+
+
+@_on_device
+def ritz_update(mode: int, which: int, first: int, rel: float, part: torch.Tensor, X: torch.Tensor, AX: torch.Tensor, W: torch.Tensor,
+                AW: Optional[torch.Tensor], P: Optional[torch.Tensor], AP: Optional[torch.Tensor], state: torch.Tensor,
+                sweep: torch.Tensor) -> None:
+    """ttr_ritz_update, in place: finishes the sums of ``part`` (what ritz_gram returned for the same vectors), solves the 3 x 3
+    pencil on the device and updates X, AX, W, P, AP; ``state`` (fp64[8]) is overwritten, ``sweep`` (fp64[4]) accumulated.
+    Nothing is read back.  See include/ttround_hip.h for the step."""
+    n = _ritz_vectors("ritz_update", X, (AX, W, AW, P, AP))
+    dt = dtype_code(X.dtype)
+    if not (part.dtype == torch.float64 and part.is_contiguous() and part.device == X.device
+            and part.numel() == 12 * ritz_parts(X.dtype, max(n, 1))):
+        raise ValueError("ritz_update: part must be the contiguous fp64 [parts, 12] tensor of ritz_gram for these vectors")
+    for t, k in ((state, 8), (sweep, 4)):
+        if not (t.dtype == torch.float64 and t.is_contiguous() and t.device == X.device and t.numel() == k):
+            raise ValueError("ritz_update: state and sweep must be contiguous fp64 device tensors of 8 and 4 elements")
+    _call("ttr_ritz_update", dt, int(mode), int(which), int(first), n, float(rel), part.data_ptr(), X.data_ptr(), AX.data_ptr(),
+          W.data_ptr(), _ptr(AW), _ptr(P), _ptr(AP), state.data_ptr(), sweep.data_ptr())

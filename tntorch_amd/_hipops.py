@@ -2382,3 +2382,20 @@ def env_update(side: str, env: torch.Tensor, G: torch.Tensor, bra: torch.Tensor,
     H = env_half_apply(env, ketT, G.permute(3, 1, 2, 0))         # [s, i, a, r']
     S, I, A, Rp = H.shape
     return gemm2d(braT.reshape(S * I, -1), H.reshape(S * I, A * Rp), transA=True).reshape(-1, A, Rp)
+
+
+# ---------------------------------------------------------------------------------------------- tt_eigsh (tteigs.py)
+RITZ_INIT, RITZ_STEP, RITZ_SA, RITZ_LA = _hip.RITZ_INIT, _hip.RITZ_STEP, _hip.RITZ_SA, _hip.RITZ_LA
+ritz_parts = _hip.ritz_parts
+ritz_workspace_bytes = _hip.ritz_workspace_bytes
+
+
+def ritz_gram(mode: int, X, AX, W=None, AW=None, P=None, AP=None) -> torch.Tensor:
+    """The fp64 partial sums [parts, 12] of the Gram pair of V = [X W P]: one launch of ttr_ritz_gram."""
+    return _hip.ritz_gram(mode, X, AX, W, AW, P, AP)
+
+
+def ritz_update(mode: int, which: int, first: int, rel: float, part: torch.Tensor, X, AX, W, AW, P, AP, state: torch.Tensor,
+                sweep: torch.Tensor) -> None:
+    """The Rayleigh-Ritz step on the six vectors, in place: one launch of ttr_ritz_update."""
+    _hip.ritz_update(mode, which, first, rel, part, X, AX, W, AW, P, AP, state, sweep)

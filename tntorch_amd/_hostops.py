@@ -1052,3 +1052,135 @@ def env_update(side: str, env: torch.Tensor, G: torch.Tensor, bra: torch.Tensor,
         raise ValueError("env_update: side must be 'left' or 'right'")
     H = env_half_apply(env, ket.permute(2, 1, 0), G.permute(3, 1, 2, 0))   # [s, i, a, r']
     return torch.einsum("ris,siab->rab", bra, H)
+
+
+# ---------------------------------------------------------------------------------------------- tt_eigsh (tteigs.py)
+# Mirror of ttr_ritz.hip: one Rayleigh-Ritz step of a three-vector LOBPCG on the vectors X, AX, W, AW, P, AP, written without a
+# branch on a value, so that the same code on device tensors is the torch baseline of tools/eigs_bench.py.
+RITZ_INIT, RITZ_STEP = 0, 1
+RITZ_SA, RITZ_LA = 0, 1
+RITZ_DROP = 64      # directions of the scaled Gram matrix below RITZ_DROP eps (of the vectors' dtype) of its largest eigenvalue go
+
+
+def ritz_parts(dtype: torch.dtype, n: int) -> int:
+    """The rows of ``part``: the mirror sums in one piece."""
+    return 1
+
+
+def ritz_workspace_bytes(dtype: torch.dtype, n: int) -> int:
+    return 12 * 8 * ritz_parts(dtype, n)
+
+
+def ritz_gram(mode: int, X, AX, W=None, AW=None, P=None, AP=None) -> torch.Tensor:
+    """part [1, 12] in fp64: S = V^T V (xx, xw, xp, ww, wp, pp) and T = V^T A V (x.ax, x.aw, x.ap, w.aw, w.ap, p.ap) of
+    V = [X W P]; RITZ_INIT fills only S_xx and T_xx, a P of None counts as zeros."""
+    d = lambda a, b: torch.dot(a.reshape(-1).double(), b.reshape(-1).double())  # noqa: E731
+    zero = torch.zeros((), dtype=torch.float64, device=X.device)
+    if mode == RITZ_INIT:
+        vals = [d(X, X)] + [zero] * 5 + [d(X, AX)] + [zero] * 5
+    else:
+        hasp = P is not None
+        vals = [d(X, X), d(X, W), d(X, P) if hasp else zero, d(W, W), d(W, P) if hasp else zero, d(P, P) if hasp else zero,
+                d(X, AX), d(X, AW), d(X, AP) if hasp else zero, d(W, AW), d(W, AP) if hasp else zero, d(P, AP) if hasp else zero]
+    return torch.stack(vals).reshape(1, 12)
+
+
+def _sym3(v):
+    """The symmetric 3 x 3 matrix of its upper triangle (00, 01, 02, 11, 12, 22)."""
+    return torch.stack([v[0], v[1], v[2], v[1], v[3], v[4], v[2], v[4], v[5]]).reshape(3, 3)
+
+
+def ritz_pencil(S: torch.Tensor, T: torch.Tensor, which: int, eps: float):
+    """The extreme Ritz pair of the 3 x 3 pencil (T, S) in fp64 -> (c [3], theta, kept, relgap).  S is scaled to unit diagonal
+    (a zero diagonal drops the direction), the eigendirections of the scaled S below ``RITZ_DROP eps`` of its largest eigenvalue
+    are dropped, and the whitened problem is solved; c is scaled to c^T S c = 1 with c[0] >= 0, theta = c^T T c.  ``relgap`` is
+    the gap between the chosen Ritz value and the next, over the spread of the kept ones (1 when one direction is kept)."""
+    d = torch.diagonal(S)
+    ok = d > 0
+    dinv = torch.where(ok, torch.where(ok, d, torch.ones_like(d)).rsqrt(), torch.zeros_like(d))
+    Ss = S * dinv[:, None] * dinv[None, :]
+    Ts = T * dinv[:, None] * dinv[None, :]
+    mu, Q = torch.linalg.eigh(Ss)
+    keep = mu > (RITZ_DROP * eps) * mu.max()
+    w = torch.where(keep, torch.where(keep, mu, torch.ones_like(mu)).rsqrt(), torch.zeros_like(mu))
+    Z = Q * w[None, :]
+    M = Z.t() @ Ts @ Z
+    if which == RITZ_LA:
+        M = -M
+    M = (M + M.t()) / 2
+    big = 2.0 * (M.abs().sum() + 1.0)
+    M = M + torch.diag(torch.where(keep, torch.zeros_like(mu), big.expand(3)))      # the dropped directions: never the smallest
+    lam, Y = torch.linalg.eigh(M)
+    c = dinv * (Z @ Y[:, 0])
+    c = c / torch.sqrt(c @ S @ c)
+    c = torch.where(c[0] < 0, -c, c)
+    theta = c @ T @ c
+    kept = keep.sum()
+    top = torch.where(torch.arange(3, device=S.device) < kept, lam, lam[0]).max()
+    relgap = torch.where(top > lam[0], (lam[1] - lam[0]) / torch.where(top > lam[0], top - lam[0], torch.ones_like(top)),
+                         torch.ones_like(top))
+    return c, theta, kept, relgap
+
+
+def ritz_update(mode: int, which: int, first: int, rel: float, part: torch.Tensor, X, AX, W, AW, P, AP, state: torch.Tensor,
+                sweep: torch.Tensor) -> None:
+    """Mirror of ttr_ritz_update, in place.  The partial sums are added in the order of their rows; the pencil is solved in fp64
+    (``ritz_pencil``); the vectors are updated in fp64 and rounded once, W = AX - theta X from the ROUNDED new X and AX.
+    RITZ_INIT: X and AX are divided by ||X||, W is set, P and AP are zeroed.  RITZ_STEP: X <- c0 X + Pn, AX <- c0 AX + APn,
+    P <- Pn = c1 W + c2 P, AP <- APn; a P of None is a zero that is neither read nor written.  A frozen step (res <= rel) or a
+    flagged one (1: a non-finite sum, 2: S_xx == 0) writes no vector and solves no pencil (c = (1, 0, 0), kept = 0).  state (fp64[8]) = theta', res, frozen, flags, c0, c1,
+    c2, kept; sweep (fp64[4]): [0] = max([0], res) when ``first``, [1] += (flags != 0), [2] = theta', [3] |= flags."""
+    dt = X.dtype
+    g = part[0].clone()
+    for r in range(1, part.shape[0]):
+        g = g + part[r]
+    S, T = _sym3(g[:6]), _sym3(g[6:])
+    finite = torch.isfinite(g).all()
+    sxx = torch.where(finite, g[0], torch.ones_like(g[0]))
+    flags = torch.where(finite, torch.zeros_like(sxx), torch.ones_like(sxx)) + torch.where(sxx == 0, 2.0, 0.0).to(sxx.dtype)
+    good = flags == 0
+    sxx = torch.where(good, sxx, torch.ones_like(sxx))
+    one, zero = torch.ones_like(sxx), torch.zeros_like(sxx)
+    if mode == RITZ_INIT:
+        inv = sxx.rsqrt()
+        theta = torch.where(good, g[6] / sxx, zero)
+        res, frozen, kept = zero, zero, torch.where(good, one, zero)     # a flagged step keeps no direction
+        c = torch.stack([torch.where(good, inv, one), zero, zero])
+        Xn = (X.double() * c[0]).to(dt)
+        AXn = (AX.double() * c[0]).to(dt)
+        Wn = (AXn.double() - theta * Xn.double()).to(dt)
+        X.copy_(Xn)
+        AX.copy_(AXn)
+        W.copy_(torch.where(good, Wn, W))
+        if P is not None:
+            P.copy_(torch.where(good, torch.zeros_like(P), P))
+            AP.copy_(torch.where(good, torch.zeros_like(AP), AP))
+    else:
+        theta0 = g[6] / sxx
+        sww = g[3]
+        res = torch.where(sww > 0, torch.sqrt(sww / torch.where(sww > 0, sww + theta0 * theta0 * sxx, one)), zero)
+        res = torch.where(good, res, zero)
+        frozen = torch.where(good & (res <= rel), one, zero)
+        eye = torch.eye(3, dtype=S.dtype, device=S.device)
+        c, theta, kept, _ = ritz_pencil(torch.where(good, S, eye), torch.where(good, T, eye), which, float(torch.finfo(dt).eps))
+        act = good & (frozen == 0)
+        theta = torch.where(act, theta, torch.where(good, theta0, zero))
+        c = torch.where(act, c, torch.stack([one, zero, zero]))
+        kept = torch.where(act, kept.to(sxx.dtype), zero)            # a frozen or flagged step solves no pencil
+        Pn = c[1] * W.double() + (c[2] * P.double() if P is not None else 0.0)
+        APn = c[1] * AW.double() + (c[2] * AP.double() if P is not None else 0.0)
+        Xn = (c[0] * X.double() + Pn).to(dt)
+        AXn = (c[0] * AX.double() + APn).to(dt)
+        Wn = (AXn.double() - theta * Xn.double()).to(dt)
+        X.copy_(torch.where(act, Xn, X))
+        AX.copy_(torch.where(act, AXn, AX))
+        W.copy_(torch.where(act, Wn, W))
+        if P is not None:
+            P.copy_(torch.where(act, Pn.to(dt), P))
+            AP.copy_(torch.where(act, APn.to(dt), AP))
+    state.copy_(torch.stack([theta, res, frozen, flags, c[0], c[1], c[2], kept.to(sxx.dtype)]))
+    if first:
+        sweep[0:1].copy_(torch.maximum(sweep[0:1], res.reshape(1)))
+    sweep[1:2].add_((flags != 0).to(sweep.dtype).reshape(1))
+    sweep[2:3].copy_(theta.reshape(1))
+    sweep[3:4].copy_(torch.where((sweep[3:4] == flags) | (flags == 0), sweep[3:4], torch.where(sweep[3:4] == 0, flags, 3.0 * one)).reshape(1))
