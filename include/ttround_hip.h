@@ -681,6 +681,15 @@ int ttr_debug_set_qr_stamps(void* device_buffer);
  *                      workgroups per CU instead of 4) and the generic build for the rest, each returning at once for the other's
  *                      items -- same results bit for bit; 0 = the generic build alone (A/B). */
 #define TTR_KNOB_SWEEP_LEAN 19
+/*   TTR_KNOB_QR_PAIR4  1 (default) = level 1 of the packed items of a fused push + factor launch of >= 256 items (fp32; the items
+ *                      whose rows 256 .. 511 are zero, see TTR_KNOB_QR_PACK_PRE) is factored by the FOUR-wave instance of the pair
+ *                      kernel: the 256 live rows as a 256-thread block, two column pairs per wave, four blocks -- four panel chains
+ *                      -- per CU where the 8-wave instance for four live row groups has two; same arithmetic in the same order,
+ *                      bit-identical results, same workspace layout; 0 = that 8-wave instance (A/B).  + 2: plain fp32 matrices of
+ *                      <= 256 rows and more than 32 columns (ttr_qr_factor) run on the four-wave pair instance too instead of the
+ *                      single-step kernel: rank-revealing pair steps, so the last bits of R differ (tests, and the A/B of the
+ *                      first core of a sweep); the workspace layout is the 4-wave one either way. */
+#define TTR_KNOB_QR_PAIR4 20
 int ttr_debug_set_knob(int knob, int value);
 int ttr_prof_enable(int on);   /* 0 = off, 1 = per-kind device times, 2 = times + executed-work census (ttr_prof_collect_work) */
 /* Synchronises the recorded events; fills total milliseconds and launch counts per kind; resets. */

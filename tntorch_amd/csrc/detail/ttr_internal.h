@@ -113,6 +113,7 @@ extern int g_qr_interleave;
 extern int g_qr_stagger;
 extern int g_qr_pack_pre;
 extern int g_qr_l1_idle;
+extern int g_qr_pair4;
 extern int g_eigh_big_occ;
 extern int g_sweep_stagger;
 extern int g_sweep_lean;

@@ -582,6 +582,10 @@ int ttr_debug_set_knob(int knob, int value) {
       g_qr_pack_pre = value & 1;
       g_qr_l1_idle = (value & 2) ? 0 : 1;
       return TTR_OK;
+    case TTR_KNOB_QR_PAIR4:
+      TTR_REQUIRE(value >= 0 && value <= 3, TTR_E_INVALID, "ttr_debug_set_knob: four-wave pair switch %d outside [0, 3]", value);
+      g_qr_pair4 = value;
+      return TTR_OK;
     case TTR_KNOB_QR_STAGGER:
       TTR_REQUIRE(value >= 0 && value <= 1024, TTR_E_INVALID, "ttr_debug_set_knob: stagger of %d kilo-cycles outside [0, 1024]", value);
       g_qr_stagger = value;

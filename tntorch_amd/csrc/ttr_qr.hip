@@ -95,9 +95,12 @@ struct QrLevel {
   // Level 1 above a PACKED pushed level 0 (8 leaf blocks, TTR_KNOB_QR_PACK = 3): the leaf flags -- rows >= m / 2 of a flagged item
   // are the absorbed leaves' R blocks, exactly zero: the NQL = NW / 2 instance of the kernel factors the upper half only and stores
   // zero reflector rows for the rest.  The level is launched twice, with the half and with the full instance; a block returns at
-  // once when its item is not of the launch's kind.  The same flags, under the same predicate, as QrApply::half_zero.  nullptr
+  // once when its item is not of the launch's kind.  (fp32: the half instance is the FOUR-wave pair block, TTR_KNOB_QR_PAIR4.)  The same flags, under the same predicate, as QrApply::half_zero.  nullptr
   // otherwise.
   const int32_t* live_half;
+  // The FOUR-wave pair instance (256-row block) only: rows of a reflector column in the workspace when that is more than the block's
+  // own 256 -- level 1 of a packed item keeps the level's [16 NT][512] layout and stores zeros in rows 256 .. 511.  0 = 256.
+  int vt_rows;
 };
 
 // beta = -sign(alpha) sqrt(alpha^2 + ss), tau = (beta - alpha)/beta, scale = 1/(alpha - beta)  (LAPACK larfg).
@@ -159,6 +162,10 @@ __device__ __forceinline__ void block_of(int grid_swap, int nb, int& b, int64_t&
 // (d += x[q] * c[q], then the wave reduction) are contracted differently by hipcc when the chain is shorter -- measured: R of a
 // 64-row block differs from its zero-padded twin's in the last digits (fp32 and fp64), while the pair kernel's packed chains,
 // which always end in a fused multiply-add before the horizontal add, compare equal.
+//
+// PAIR with NW = 4 (fp32, not pushed): the NQL = 4 instance's live rows as a block of their own -- 256 rows, four waves, wave w
+// owning panel columns 4w .. 4w + 3 as the two pairs 2w, 2w + 1, each held as the same row pairs.  Same arithmetic in the same
+// order (bit-identical R, reflectors and T); what changes is what a CU holds: four blocks, i.e. four panel chains, instead of two.
 template <typename T, int NT, bool PUSHED, int NW, bool PAIR, int NQL = NW>
 __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_kernel(QrLevel<T> p) {
   static_assert(NQL == NW || (PAIR && !PUSHED && NQL >= 4 && NQL < NW && (NQL & 1) == 0), "live 64-row groups of the block");
@@ -184,7 +191,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
   T* const Xp = WXs;
   __shared__ T Xs[PW * VLD];                                    // scratch of the recursive T construction
   __shared__ T W2s[PW][NP + 1];
-  __shared__ T pairt[NW];                                       // PAIR: v0^T v1 of every owner's pair
+  __shared__ T pairt[PAIR ? PW / 2 : NW];                       // PAIR: v0^T v1 of every pair of the panel
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -576,7 +583,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
   } else {
     // level 1 of packed and unpacked items: one launch of the half-block instance, one of the full one; each item is taken by one
     if constexpr (PAIR) {
-      if (p.live_half && (p.live_half[bt] == 3) != (NQL < NW)) return;
+      if (p.live_half && (p.live_half[bt] == 3) != (NQL < NW || NW == 4)) return;
     }
     const T* __restrict__ X = p.X + bt * p.strideX + row0 * p.ldx;
 #pragma unroll
@@ -734,7 +741,9 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
 #define TTR_WSTAMP(pn, k4)
 #endif
   const int64_t blk = bt * p.nb + b;
-  T* __restrict__ Vt = p.Vt + blk * (int64_t)NP * BR;
+  int BRS = BR;   // rows of a reflector column in the workspace
+  if constexpr (PAIR && NW == 4) { if (p.vt_rows > BR) BRS = p.vt_rows; }
+  T* __restrict__ Vt = p.Vt + blk * (int64_t)NP * BRS;
   T* __restrict__ tau = p.tau + blk * (int64_t)NP;
   T* __restrict__ Tg = p.Tg + blk * (int64_t)NT * PW * PW;
   if (tid < NP) taus[tid] = T(0);
@@ -762,6 +771,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
     // operation of a Householder step is then a packed two-row instruction -- the step chain is bound by the number of
     // instructions the one active wave has to issue (~8 cycles each, measured), not by their width
     V2 pcv[2][NW / 2];
+    V2 pcq[2][2][NW / 2];   // PAIR, four waves: the wave's two pairs, pcq[0] = pair 2w, pcq[1] = pair 2w + 1, each as pcv
     // PAIR: no barrier before this store -- the previous panel's update only reads the wave's OWN rows of Vs (A operand of
     // A2 += V W2), which are the rows it rewrites here; the single-step variant's owners write other waves' rows early
     if constexpr (!PAIR) { if (pnl > 0) lds_barrier(); }  // the previous panel's MFMA update may still be reading Vs
@@ -791,7 +801,40 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
       for (int h = 2; h < NHL; ++h) e = __builtin_elementwise_fma(x[h], y[h], e);
       return e;
     };
-    if constexpr (PAIR) {
+    if constexpr (PAIR && NW == 4) {
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr)
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+          for (int q = 0; q < NW; ++q) pcq[pr][cc][q >> 1][q & 1] = Vs[(lane + 64 * q) * VLD + wave_id * 4 + pr * 2 + cc];
+      // what is left of this panel, as below: one partial per PAIR (two slots per wave), summed in pair order
+      {
+        T e2[2];
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+          T e = T(0);
+#pragma unroll
+          for (int cc = 0; cc < 2; ++cc) {
+            V2 xl[NW / 2];
+            xl[0] = pcq[pr][cc][0];
+            if (lane < j0) xl[0].x = T(0);
+            xl[1] = pcq[pr][cc][1];
+            const V2 a2 = dotp(IC<0>{}, xl, xl);
+            e += a2.x + a2.y;
+          }
+          e2[pr] = wave_sum_dpp(e);
+        }
+        if (lane == 0) { pairt[2 * wave_id] = e2[0]; pairt[2 * wave_id + 1] = e2[1]; }
+        lds_barrier();
+        T pr2 = pairt[0];
+#pragma unroll
+        for (int w = 1; w < PW / 2; ++w) pr2 += pairt[w];
+        rank_skip = lane_get(pr2, 0) <= rank_thr;   // block-uniform, scalar
+        lds_barrier();                     // pairt is rewritten by the owners
+        if (rank_skip) nsteps = 0;
+      }
+    } else if constexpr (PAIR) {
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
@@ -874,7 +917,8 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
       // its left (barrier, apply their pair), then its own (factor, publish, barrier, deferred stores), then only the
       // barriers of the owners to its right.  One loop with all three roles under branches made the register allocator
       // keep the columns in two register sets and copy all 16 values back and forth in every phase.
-      static_assert(!PAIR || (CPW == 2 && NW == 8), "PAIR: two columns per wave, eight waves");
+      static_assert(!PAIR || (CPW == 2 && NW == 8) || (CPW == 4 && NW == 4 && !PUSHED && sizeof(T) == 4),
+                    "PAIR: one pair per wave of eight, or (fp32, not pushed) two pairs per wave of four");
       constexpr int NH = NW / 2;
       // the exchange slot of a lane: v0's pairs in words 0 .. 7, v1's in words 8 .. 15; only the pieces that hold live pairs travel
       auto xput = [&](T* xs, const V2 (&a)[NH], const V2 (&c)[NH]) {
@@ -903,6 +947,165 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
           c[2] = *reinterpret_cast<const V2*>(xs + 12);
         }
       };
+      if constexpr (NW == 4) {
+      // FOUR waves: wave w owns pairs A = 2w and B = 2w + 1.  Still one phase and one barrier per pair, every wave its own sequence:
+      // the phases of the pairs to its left (barrier, apply the pair to A and to B), then A (factor, publish, barrier), B (apply A
+      // with the applier's formula -- what the wave that owns B alone does in the 8-wave block --, factor, publish, barrier), the
+      // deferred stores of both, then the S blocks of A and of B under the barriers of the pairs to its right.  A's reflectors
+      // stay in registers across B's phase (8 VGPRs at two row pairs): its exchange slot is rewritten after the next barrier.
+      const int nph = (nsteps + 1) >> 1;            // phases = column pairs that take a step (block-uniform)
+      const int pa = wave_id * 2, pb = pa + 1;
+      const bool mineA = pa < nph, mineB = pb < nph;
+      const int napply = mineA ? pa : nph;
+      const bool liveA = j0 + pa * 2 < n, liveB = j0 + pb * 2 < n;   // the pair's columns exist
+      auto slot = [&](int k) { return Xp + (k & 1) * (64 * XLD) + lane * XLD; };
+      // apply H1 H0 of a published pair to one of the wave's pairs
+      auto apply_pair = [&](const V2 (&w0)[NH], const V2 (&w1)[NH], T ta, T tb, T t12, V2 (&c)[2][NH]) {
+        const V2 e0 = dotp(IC<1>{}, w0, c[0]), e1 = dotp(IC<1>{}, w0, c[1]);
+        const V2 e2 = dotp(IC<1>{}, w1, c[0]), e3 = dotp(IC<1>{}, w1, c[1]);
+        T d4[4] = {e0.x + e0.y, e1.x + e1.y, e2.x + e2.y, e3.x + e3.y};
+        wave_sum4(d4);
+        const T a0a = ta * d4[0], a0b = ta * d4[1];
+        const T a1a = tb * (d4[2] - t12 * a0a), a1b = tb * (d4[3] - t12 * a0b);
+#pragma unroll
+        for (int h = 0; h < NHL; ++h) {
+          c[0][h] = (c[0][h] - a0a * w0[h]) - a1a * w1[h];
+          c[1][h] = (c[1][h] - a0b * w0[h]) - a1b * w1[h];
+        }
+      };
+      // factor the pair at panel columns j, j + 1 (the owner's steps of the 8-wave block) and publish it
+      auto factor_pair = [&](V2 (&c)[2][NH], int pk, V2 (&v0)[NH], V2 (&v1)[NH], T& t0, T& t1, T& t12) {
+        const int j = pk * 2, jj = j0 + j, jj1 = jj + 1;
+        const bool two = j + 1 < nsteps;  // the second column of the pair takes a step as well
+        t0 = T(0); t1 = T(0); t12 = T(0);
+        // ---- column 0: x0 = sub-column below the pivot; ||x0||^2 and x0 . c1 in one 2-value reduction
+        V2 x0[NH];
+        x0[0] = c[0][0];
+        if (!(lane > jj)) x0[0].x = T(0);
+#pragma unroll
+        for (int h = 1; h < NHL; ++h) x0[h] = c[0][h];
+        const V2 e00 = dotp(IC<0>{}, x0, x0), e01 = dotp(IC<1>{}, x0, c[1]);
+        T s00 = e00.x + e00.y, s01 = e01.x + e01.y;
+        wave_sum2(s00, s01);
+        const T alpha0 = lane_get(c[0][0].x, jj);
+        T beta0, sc0;
+        if (s00 < Num<T>::larfg_floor()) { beta0 = alpha0; t0 = T(0); sc0 = T(0); }  // LAPACK larfg: H = I
+        else larfg_scalars(alpha0, s00, beta0, t0, sc0);
+#pragma unroll
+        for (int h = 0; h < NHL; ++h) v0[h] = x0[h] * sc0;
+        if (!(lane > jj)) v0[0].x = (lane == jj) ? T(1) : T(0);
+        {  // H0 on column 1: v0^T c1 = sc0 * x0^T c1 + c1[jj]
+          const T f = t0 * (sc0 * s01 + lane_get(c[1][0].x, jj));
+#pragma unroll
+          for (int h = 0; h < NHL; ++h) c[1][h] = c[1][h] - f * v0[h];
+        }
+        if (lane == jj) c[0][0].x = beta0;  // R[jj][jj]
+        // ---- column 1: ||x1||^2 and v0 . x1 (for v0^T v1) in one 2-value reduction
+        if (two) {
+          V2 x1[NH];
+          x1[0] = c[1][0];
+          if (!(lane > jj1)) x1[0].x = T(0);
+#pragma unroll
+          for (int h = 1; h < NHL; ++h) x1[h] = c[1][h];
+          const V2 e11 = dotp(IC<0>{}, x1, x1), e0v = dotp(IC<0>{}, v0, x1);
+          T s11 = e11.x + e11.y, s0v = e0v.x + e0v.y;
+          wave_sum2(s11, s0v);
+          const T alpha1 = lane_get(c[1][0].x, jj1);
+          T beta1, sc1;
+          if (s11 < Num<T>::larfg_floor()) { beta1 = alpha1; t1 = T(0); sc1 = T(0); }
+          else larfg_scalars(alpha1, s11, beta1, t1, sc1);
+#pragma unroll
+          for (int h = 0; h < NHL; ++h) v1[h] = x1[h] * sc1;
+          if (!(lane > jj1)) v1[0].x = (lane == jj1) ? T(1) : T(0);
+          t12 = sc1 * s0v + lane_get(v0[0].x, jj1);  // v1 = sc1 * x1 below row jj1, 1 on it
+          if (lane == jj1) c[1][0].x = beta1;
+        } else {
+#pragma unroll
+          for (int h = 0; h < NHL; ++h) v1[h] = V2{T(0), T(0)};
+        }
+        xput(slot(pk), v0, v1);
+        if (lane == 0) { taus[jj] = t0; taus[jj1] = t1; pairt[pk] = t12; }
+      };
+      // after the pair's barrier.  The scalars (lane 0): tau, and the pair's own block of T = (strict_upper(V^T V) + diag(1 / tau))^-1
+      // and of S = V^T V -- wave 0's t_columns reads them one barrier later, so they cannot wait for the deferred stores
+      auto pair_scalars = [&](int pk, T t0, T t1, T t12) {
+        const int j = pk * 2;
+        if (lane == 0) {
+          tau[j0 + j] = t0; tau[j0 + j + 1] = t1;
+          Ts[j * VLD + j] = t0; Ts[(j + 1) * VLD + j + 1] = t1; Ts[j * VLD + j + 1] = -t0 * t12 * t1;
+          Ss[j * VLD + j + 1] = t12;
+        }
+      };
+      // off the chain: the reflectors go to the [row][j] panel image the MFMA phases read, and to the workspace
+      auto store_pair = [&](int pk, const V2 (&v0)[NH], const V2 (&v1)[NH]) {
+        const int j = pk * 2;
+#pragma unroll
+        for (int q = 0; q < NW; ++q) {
+          const T a = v0[q >> 1][q & 1], c = v1[q >> 1][q & 1];
+          Vs[(lane + 64 * q) * VLD + j] = a;
+          Vs[(lane + 64 * q) * VLD + j + 1] = c;
+          Vt[(int64_t)(j0 + j) * BRS + lane + 64 * q] = a;
+          Vt[(int64_t)(j0 + j + 1) * BRS + lane + 64 * q] = c;
+        }
+      };
+      // the 2 x 2 block S[pair pk][pair k] = V_pk^T V_k, one 4-value reduction
+      auto s_block = [&](int pk, const V2 (&u0)[NH], const V2 (&u1)[NH], int k, const V2 (&w0)[NH], const V2 (&w1)[NH]) {
+        const int j = pk * 2;
+        const V2 e0 = dotp(IC<1>{}, u0, w0), e1 = dotp(IC<1>{}, u0, w1);
+        const V2 e2 = dotp(IC<1>{}, u1, w0), e3 = dotp(IC<1>{}, u1, w1);
+        T d4[4] = {e0.x + e0.y, e1.x + e1.y, e2.x + e2.y, e3.x + e3.y};
+        wave_sum4(d4);
+        if (lane == 0) {
+          Ss[j * VLD + 2 * k] = d4[0]; Ss[j * VLD + 2 * k + 1] = d4[1];
+          Ss[(j + 1) * VLD + 2 * k] = d4[2]; Ss[(j + 1) * VLD + 2 * k + 1] = d4[3];
+        }
+      };
+      __builtin_amdgcn_s_setprio(3);
+      for (int owv = 0; owv < napply; ++owv) {
+        const int jj = j0 + owv * 2;
+        lds_barrier();  // the owner's pair (exchange slot), its taus and v0^T v1 are visible
+        if (liveA) {
+          V2 w0[NH], w1[NH];
+          xget(slot(owv), w0, w1);
+          const T ta = taus[jj], tb = taus[jj + 1], t12 = pairt[owv];
+          apply_pair(w0, w1, ta, tb, t12, pcq[0]);
+          if (liveB) apply_pair(w0, w1, ta, tb, t12, pcq[1]);
+        }
+      }
+      if (mineA) {
+        V2 u0[NH], u1[NH];
+        T ua, ub, uab;
+        factor_pair(pcq[0], pa, u0, u1, ua, ub, uab);
+        lds_barrier();
+        pair_scalars(pa, ua, ub, uab);
+        if (mineB) {
+          V2 x0[NH], x1[NH];
+          T xa, xb2, xab;
+          apply_pair(u0, u1, ua, ub, uab, pcq[1]);
+          factor_pair(pcq[1], pb, x0, x1, xa, xb2, xab);
+          lds_barrier();
+          pair_scalars(pb, xa, xb2, xab);
+          store_pair(pa, u0, u1);
+          store_pair(pb, x0, x1);
+          // the phases of the pairs to the right, at priority 0: S blocks, and wave 0's T columns one pair behind
+          __builtin_amdgcn_s_setprio(0);
+          s_block(pa, u0, u1, pb, x0, x1);
+          for (int k = pb + 1; k < nph; ++k) {
+            lds_barrier();
+            {
+              V2 w0[NH], w1[NH];
+              xget(slot(k), w0, w1);
+              s_block(pa, u0, u1, k, w0, w1);
+              s_block(pb, x0, x1, k, w0, w1);
+            }
+            if (pa == 0) t_columns(k - 1);
+          }
+        } else {
+          store_pair(pa, u0, u1);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      } else {
       const int nph = (nsteps + 1) >> 1;            // phases = column pairs that take a step (block-uniform)
       const bool mine = wave_id < nph;
       const int napply = mine ? wave_id : nph;
@@ -1046,6 +1249,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
         }
       }
       __builtin_amdgcn_s_setprio(0);
+      }
     } else {
     for (int owv = 0; owv < NW; ++owv) {
       if (owv * CPW < nsteps) {  // block-uniform
@@ -1142,7 +1346,8 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
         const int c = j0 + wave_id * CPW + cc;
         if (c < n && lane < rr) {
           T rv;
-          if constexpr (PAIR) rv = (lane <= c && lane < kb) ? (cc == 0 ? pcv[0][0].x : pcv[1][0].x) : T(0);
+          if constexpr (PAIR && NW == 4) rv = (lane <= c && lane < kb) ? pcq[cc >> 1][cc & 1][0].x : T(0);
+          else if constexpr (PAIR) rv = (lane <= c && lane < kb) ? (cc == 0 ? pcv[0][0].x : pcv[1][0].x) : T(0);
           else rv = (lane <= c && lane < kb) ? pc[cc][0] : T(0);
           if constexpr (sizeof(T) == 4) { if (bexp != 0 && !(!PUSHED && p.top && p.expo_acc)) rv = ldexpf((float)rv, bexp); }
           Ro[(int64_t)lane * p.ldr + c] = rv;
@@ -1153,7 +1358,14 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
       // the owners stored their pairs themselves; columns no phase covered are identity reflectors
       // (a rank-skipped panel is recognised by its zero taus: the apply kernel never reads its reflectors or its T)
       if (!rank_skip)
-        for (int j = (nsteps + 1) & ~1; j < PW; ++j) Vt[(int64_t)(j0 + j) * BR + tid] = T(0);
+        for (int j = (nsteps + 1) & ~1; j < PW; ++j) Vt[(int64_t)(j0 + j) * BRS + tid] = T(0);
+      if constexpr (NW == 4) {   // workspace contract: the rows the level's layout has beyond the block are stored, as zeros, off the chain
+        if (!rank_skip && BRS > BR) {
+#pragma unroll
+          for (int j = 0; j < PW; ++j)
+            for (int r = BR + tid; r < BRS; r += NTH) Vt[(int64_t)(j0 + j) * BRS + r] = T(0);
+        }
+      }
       if (tid < PW && tid >= ((nsteps + 1) & ~1)) tau[j0 + tid] = T(0);
     } else {
       for (int j = nsteps; j < PW; ++j) {  // identity reflectors: keep the stored factors well defined
@@ -1826,6 +2038,25 @@ static void factor_launch(int nlq, dim3 grid, hipStream_t stream, const QrLevel<
   else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 4>), grid, dim3(512), 0, stream, p);
 }
 
+// ttr_debug_set_knob(TTR_KNOB_QR_PAIR4).  Bit 0 (default): level 1 of the packed items of a launch (QrLevel::live_half) runs on the
+// FOUR-wave pair instance -- the 256 live rows as a 256-thread block, four blocks and so four panel chains per CU where the 8-wave
+// NQL = 4 instance has two; bit-identical.  Bit 1: plain fp32 matrices of <= 256 rows and more than 32 columns as well (rank-revealing
+// pair steps instead of the single-step kernel: the last bits of R differ; the tests' hook, and the first core's A/B).
+int g_qr_pair4 = 1;
+
+// The four-wave pair instance (fp32, 64 columns) over `grid` in 256-thread blocks, writing reflector columns of `vt_rows` rows;
+// false when `want` is off or the instance does not exist for <T, NT>: the caller launches what it launched before.
+template <typename T, int NT>
+static bool pair4_launch(bool want, int vt_rows, dim3 grid, hipStream_t stream, QrLevel<T> p) {
+  if constexpr (sizeof(T) == 4 && NT == 4) {
+    if (!want) return false;
+    p.vt_rows = vt_rows;
+    hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, true>), grid, dim3(256), 0, stream, p);
+    return true;
+  }
+  return false;
+}
+
 template <typename T, int NT>
 static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, int64_t strideA, T* R, int64_t ldr,
                       int64_t strideR, T* ws, const QrPlan& pl, const Pushed& pu, hipStream_t stream, int64_t a_cs = 1) {
@@ -1851,6 +2082,7 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
     p.top = (l == L - 1);
     p.expo_acc = (p.top && !(l == 0 && pu.Rm)) ? pu.expo_acc : nullptr;
     p.stagger_kc = g_qr_stagger;
+    p.vt_rows = 0;
     // (from g_qr_pack_pre_min items on, like the packing decision ahead of the launch: the level then costs two launches, one of
     // which only returns -- in a latency-bound small-batch sweep that launch costs what the shorter chain saves)
     p.live_half = (l1_half_zero(pl, l, n, pu.Rm != nullptr) && g_qr_variant != 0 && batch >= g_qr_pack_pre_min)
@@ -1877,14 +2109,17 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
       const int nlq = (int)ceil_div(rows_max, (int64_t)16 * pl.nw[l]);
       if (pl.nw[l] == 8 && g_qr_variant != 0) {
         if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, true>), grid, dim3(512), 0, stream, p);
-        else if (p.live_half) { factor_launch<T, NT>(2, grid, stream, p); factor_launch<T, NT>(4, grid, stream, p); }   // packed items, the rest
-        else factor_launch<T, NT>(nlq, grid, stream, p);
+        else if (p.live_half) {   // packed items, then the rest
+          if (!pair4_launch<T, NT>((g_qr_pair4 & 1) != 0, 64 * pl.nw[l], grid, stream, p)) factor_launch<T, NT>(2, grid, stream, p);
+          factor_launch<T, NT>(4, grid, stream, p);
+        } else factor_launch<T, NT>(nlq, grid, stream, p);
       } else if (pl.nw[l] == 8) {
         if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, false>), grid, dim3(512), 0, stream, p);
         else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, false>), grid, dim3(512), 0, stream, p);
       } else {
         if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 4, false>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, false>), grid, dim3(256), 0, stream, p);
+        else if (!pair4_launch<T, NT>((g_qr_pair4 & 2) != 0 && L == 1 && g_qr_variant != 0, 256, grid, stream, p))   // (the test hook)
+          hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, false>), grid, dim3(256), 0, stream, p);
       }
     }
     if (work_census_on()) {   // what this launch executed, from the taus / flags it left behind (outside the timed scope)
