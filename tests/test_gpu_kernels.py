@@ -961,6 +961,40 @@ def test_batch_above_grid_limit():
     assert (Y - X * sc[:, None, :]).abs().max().item() < 1e-6
 
 
+@pytest.mark.gpu
+def test_pushed_batch_above_grid_limit():
+    """A PUSHED factorisation of more than 65535 items and its apply: the slices offset Rm / the core(s) / expo_acc / R / C / Out per
+    slice and lay their workspaces (reflectors, T factors, flag words) one after the other.  The sliced call has to equal, bit for
+    bit, two calls on the items [:65535] and [65535:] -- for the fused push (with expo_acc) and for the fused push of a sum."""
+    h = _hip()
+    S, B = 65535, 65535 + 2
+    k, Rin, I, n, kc = 4, 4, 2, 4, 3   # one 256-row block per item, 16 padded columns: ~1 GB of workspace for the batch
+    g = torch.Generator().manual_seed(65537)
+    Rm = torch.randn(B, k, Rin, generator=g).cuda()
+    core = torch.randn(B, Rin, I, n, generator=g).cuda()
+    C = torch.randn(B, n, kc, generator=g).cuda()
+
+    def pushed(sl):
+        ex = torch.zeros(Rm[sl].shape[0], dtype=torch.int32, device="cuda")
+        f = h.qr_factor_pushed(Rm[sl].contiguous(), core[sl].contiguous(), expo_acc=ex)
+        return f.R, ex, h.qr_apply(f, C[sl].contiguous())
+
+    def pushed_sum(sl):   # ra = rb = 2, ca = cb = 2
+        a, b = core[sl, :2, :, :2].contiguous(), core[sl, 2:, :, 2:].contiguous()
+        f = h.qr_factor_pushed_sum(Rm[sl].contiguous(), a, b)
+        return f.R, h.qr_apply(f, C[sl].contiguous())
+
+    for run in (pushed, pushed_sum):
+        whole = run(slice(None))
+        first = run(slice(0, S))
+        second = run(slice(S, B))
+        for w, p, q in zip(whole, first, second):
+            assert w.shape[0] == B and torch.isfinite(w.float()).all()
+            assert torch.equal(w, torch.cat([p, q])), run.__name__
+        assert whole[0].abs().max().item() > 0
+        del whole, first, second
+
+
 @pytest.mark.parametrize("Rin,I,n", [(64, 64, 64), (64, 8, 64), (40, 24, 32), (64, 16, 48)])
 def test_qr_apply_pushed_gram(Rin, I, n):
     """ttr_qr_apply_pushed_gram: the apply kernel's own row Gram matrix of its output (round.py:104-109 fused into the

@@ -155,7 +155,7 @@ __device__ __forceinline__ void block_of(int grid_swap, int nb, int& b, int64_t&
 // rows), or level 1 of a packed item (QrLevel::live_half).  The rows below are exact zeros and stay so (0 * x, x + 0): in the
 // column-owning layout nobody multiplies them, and a wave whose own 64 rows are dead (wave >= NQL) skips its share of the MFMA
 // phases.  Sums keep their order over the live terms, so the result is bit-identical to carrying the zeros along.  A template
-// parameter, chosen by the host per launch (factor_launch): a runtime bound puts a branch into every unrolled loop of the step
+// parameter, chosen by the host per launch (factor_instances): a runtime bound puts a branch into every unrolled loop of the step
 // chain, and several compile-time variants inside ONE kernel spill (hipcc: 95 - 440 spilled registers for two to four variants
 // of the 64-column instances, none for any single one).
 // NOT for the single-step kernels (PAIR = false), and at least two row pairs: their scalar dot-product chains
@@ -389,131 +389,8 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 ? 4 : 1)) void qr_factor_k
           (void)run_pass(-1);
         }
       };
-#ifdef TTR_QR_PUSH_KSTEP
-      // Round 6, measured WITHOUT gain and therefore not compiled by default (tools/build_variant.sh kstep ttr_qr.hip
-      // -DTTR_QR_PUSH_KSTEP; profiles/r06_push_variants.txt): the K-STEP pipeline (whole shapes with a multiple of 8 K steps; fp32
-      // 8-wave PAIR blocks -- the metric's).  Hypothesis: since row packing a pass performs half the MFMAs per byte it loads, and
-      // the group pipeline above -- 16 loads, then a burst of 32 MFMAs during which ONE group is in flight -- would run at one
-      // memory round trip per group.  Here the 32 operand registers are EIGHT K-step slots: step t is consumed from slot t mod 8 and
-      // the slot is refilled at once with step t + 8 (of the next pass when this one ends), so two groups' worth of loads stay in
-      // flight through the MFMAs; same MFMAs in the same order: bit-identical (sha256 of R); a block that may turn out absorbed
-      // requests nothing before it knows (the group pipeline fetches and drops 32 KB).  Result: push 41 - 45 k cycles against
-      // 38 - 45 k, the step 24.88 against 24.89 ms.  The depth of the prefetch is not what paces the phase (push_membench: 1, 2 or 4
-      // groups in flight move the same bytes in the same 12.8 k ticks); without ANY MFMA (-DTTR_QR_PUSH_NOMMA) the phase still takes
-      // 24 k cycles alone on a CU and 37 k under load: ~9 k of fixed work (R staged through LDS, the range guard and the block norm:
-      // five block-wide barriers) + 256 KB at the ~17 B/clk one CU's load path sustains on this pattern.
-      auto stream_ks = [&]() {
-        constexpr int NS = 8;
-        T bq[NS][NT];
-        const T* __restrict__ ldp = Cb + (size_t)imode_u * n + loff;   // the loader's position: lane pointer, advanced per K step
-        const size_t kstride = (size_t)4 * cs;
-        auto load_slot = [&](T (&bs)[NT]) {
-#pragma unroll
-          for (int tn = 0; tn < NT; ++tn) bs[tn] = ldp[tn * PW];
-          ldp += kstride;
-        };
-        const bool may_absorb = p.pack_ok && p.rank_skip_c > 0 && p.pk == 64 && (p.nb & 1) == 0 && p.pI == NW * p.nb && absorbed_blk;
-        bool upper = false;
-        auto decide = [&]() {   // after the barrier that publishes Rs and the waves' partial sums
-          T any = pairt[0], sa = Ss[0], sl = Ss[NW];
-#pragma unroll
-          for (int w = 1; w < NW; ++w) { any += pairt[w]; sa += Ss[w]; sl += Ss[NW + w]; }
-          upper = any == T(0);
-          const T ce = T(p.rank_skip_c) * Num<T>::eps();
-          packed = p.pack_ok && p.rank_skip_c > 0 && p.pk == 64 && (p.nb & 1) == 0 && p.pI == NW * p.nb &&
-                   lane_get(sl, 0) <= ce * ce * lane_get(sa, 0);
-        };
-        // A block that may be absorbed decides first and requests its slots afterwards; every other block requests them first (in
-        // flight while Rs is staged).  ONE copy of the 32 requests, in slot order (scheduling barriers): the loop's static vmcnt
-        // counts must hold on the entry path too -- with two copies hipcc ordered one of them differently and every first slot of an
-        // iteration waited for all but 4 loads.
-        if (may_absorb) {
-          lds_barrier();
-          decide();
-          if (packed) return;
-        }
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) { load_slot(bq[sl]); __builtin_amdgcn_sched_barrier(0); }
-        if (!may_absorb) {
-          lds_barrier();
-          decide();
-        }
-#pragma unroll
-        for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < NT; ++tn) acc[tm][tn] = M::zero();
-        const int total = packed ? 2 * ksteps : ksteps;   // K steps over both passes (multiples of NS)
-        int t_ld = NS;                                    // next step to request
-        // NS steps: consume slot sl, refill it with step t + NS.  REFILL is a compile-time property of the iteration -- every
-        // iteration but the last refills all its slots -- because hipcc's s_waitcnt insertion only keeps the loads counted
-        // (vmcnt(28) before a slot's first MFMA: seven slots stay in flight) when every path through the loop body issues the same
-        // loads in the same order; with the refill under a branch it waited for vmcnt(0) at every slot.
-        auto steps8 = [&](int t0, auto REFILL) {
-          constexpr bool kRefill = decltype(REFILL)::value != 0;
-          const bool second = t0 >= ksteps;               // packed: the absorbed block's mode index into row tiles 2, 3
-          const int tm_lo = second ? 2 : 0, tm_hi = packed ? tm_lo + 2 : 4, tm_sub = tm_lo;
-          const int ks0 = second ? t0 - ksteps : t0;
-#pragma unroll
-          for (int sl = 0; sl < NS; ++sl) {
-            const int ks = ks0 + sl, grp = ks >> 2;
-            const int r0 = ks * 4 + g;
-            T av[4];
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm) av[tm] = Rs[(tm * 16 + cl) * RLD + r0];
-#if defined(TTR_QR_PUSH_NOMMA)
-            // (diagnostics build: the push without its MFMAs -- what do the loads and the rest of the phase cost?  wrong results)
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) asm volatile("" ::"v"(bq[sl][tn]), "v"(av[tn]));
-#elif defined(TTR_QR_PUSH_ZSKIP)
-            // (-DTTR_QR_PUSH_ZSKIP, measured SLOWER: push 53 - 57 k instead of 42 - 45 k cycles -- the compare + ballot + branch per tile
-            // cost the waves more issue time than the skipped MFMAs free on the pipe.)  Zero operand tiles are not multiplied: the cores of a SUM of trains (tensor.py:445-668: blockdiag(a, b), what rounding
-            // is mostly called on) are half zeros, and a 4 x 16 B tile that is zero in every lane adds nothing to its accumulators
-            // (x + a * 0 = x: bit-identical for finite R).  One compare + ballot per tile, against two MFMAs (64 cycles of the
-            // SIMD's matrix pipe, which BOTH resident blocks' pushes share -- the pipe, not HBM, paces the phase).
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) {
-              if (__ballot(bq[sl][tn] != T(0)) == 0ull) continue;   // wave-uniform
-#pragma unroll
-              for (int tm = 0; tm < 4; ++tm) {
-                if (tm < tm_lo || tm >= tm_hi) continue;       // wave-uniform
-                if (upper && grp < tm - tm_sub) continue;      // wave-uniform (upper-triangular Rm: zero K groups)
-                acc[tm][tn] = M::mma(tm_sub == 0 ? av[tm] : av[tm & 1], bq[sl][tn], acc[tm][tn]);
-              }
-            }
-#else
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm) {
-              if (tm < tm_lo || tm >= tm_hi) continue;       // wave-uniform
-              if (upper && grp < tm - tm_sub) continue;      // wave-uniform (upper-triangular Rm: zero K groups)
-#pragma unroll
-              for (int tn = 0; tn < NT; ++tn) acc[tm][tn] = M::mma(tm_sub == 0 ? av[tm] : av[tm & 1], bq[sl][tn], acc[tm][tn]);
-            }
-#endif
-            if constexpr (kRefill) {
-              // (the second pass begins: a select on the pointer, not a branch around the loads)
-              const T* __restrict__ p2 = Cb + (size_t)(NW * partner_blk + wave_id) * n + loff;
-              ldp = (t_ld == ksteps) ? p2 : ldp;
-              load_slot(bq[sl]);
-              ++t_ld;
-            }
-          }
-        };
-        int t0 = 0;
-        for (; t0 + NS < total; t0 += NS) steps8(t0, IC<1>{});
-        steps8(t0, IC<0>{});
-      };
-      if constexpr (NW == 8 && PAIR && sizeof(T) == 4) {
-        if (full && (ksteps & 7) == 0) stream_ks();
-        else if (full) stream(IC<1>{});
-        else stream(IC<0>{});
-      } else {
-        if (full) stream(IC<1>{});
-        else stream(IC<0>{});
-      }
-#else
       if (full) stream(IC<1>{});
       else stream(IC<0>{});
-#endif
       if (packed && absorbed_blk) {
         // an absorbed block: its rows live in its partner block.  The level above reads this block's R: zeros; its reflectors are
         // H = I (zero taus: the apply kernel returns at once for it)
@@ -1865,102 +1742,7 @@ __global__ __launch_bounds__(64 * NW, (sizeof(T) == 4 && NW == 8 ? 4 : 1)) void 
   astamp();
 }
 
-// ---------------------------------------------------------------- host-side tree
-struct QrPlan {
-  int levels;
-  int npad;  // 16 * NT
-  int64_t m[16];
-  int nb[16];
-  int nw[16];  // waves per block on this level (block rows = 64 * nw)
-  // workspace offsets in elements
-  int64_t off_vt[16], off_tau[16], off_tg[16], off_x[16], off_out[16];
-  int64_t off_flag;  // one int32 per item (stored in an element slot): level-0 row packing of a pushed factorisation
-  int64_t total;  // elements
-};
-
-static int nt_for(int64_t n) { return n <= 16 ? 1 : (n <= 32 ? 2 : 4); }
-int g_qr_f64_nw4 = 0;  // ttr_debug_set_knob(TTR_KNOB_QR_F64_NW4): fp64 trees out of 256-row (4-wave) blocks only
-// fp64: the 8-wave block needs 132 KB of LDS and 237 VGPRs (ONE block, i.e. one Householder chain, per CU); two 4-wave
-// blocks would fit (75 KB, 2 waves per SIMD).  Measured on config C2's resident batch (tools/c2_ab.py): 256 trains in
-// 40.9 ms with the 4-wave blocks against 34.0 ms with the 8-wave blocks (qr_factor 37.1 vs 25.5 ms) -- the pair phases of
-// the 8-wave block and the shallower tree outweigh the second chain per CU.  Kept as a switch, off.
-// (bit 1 of the switch: the same for fp32 -- round 4's A/B of "256-row leaves x 4 waves, four blocks per CU" on the metric)
-static bool nw4_forced(bool f64) { return f64 ? (g_qr_f64_nw4 & 1) != 0 : (g_qr_f64_nw4 & 2) != 0; }
-// (bit 2 of the knob, A/B: fp32 matrices of <= 256 rows on the 8-wave PAIR kernel too -- its panels are rank-revealing, the 4-wave kernel's are not)
-static int nw_for(int64_t rows, bool f64) { return ((rows > BR4 || (!f64 && (g_qr_f64_nw4 & 4) != 0)) && !nw4_forced(f64)) ? 8 : 4; }
-
-static QrPlan make_plan(int64_t m, int64_t n, int64_t batch, bool f64) {
-  QrPlan pl{};
-  const int NT = nt_for(n);
-  pl.npad = NT * PW;
-  int64_t cur = m;
-  int L = 0;
-  for (;;) {
-    pl.m[L] = cur;
-    pl.nw[L] = nw_for(cur, f64);
-    pl.nb[L] = (int)ceil_div(cur, 64 * pl.nw[L]);
-    ++L;
-    if (pl.nb[L - 1] <= 1) break;
-    cur = (int64_t)pl.nb[L - 1] * n;
-  }
-  pl.levels = L;
-  int64_t off = 0;
-  for (int l = 0; l < L; ++l) {
-    pl.off_vt[l] = off; off += batch * pl.nb[l] * pl.npad * 64 * pl.nw[l];
-    pl.off_tau[l] = off; off += align_up(batch * pl.nb[l] * pl.npad, 64);
-    pl.off_tg[l] = off; off += batch * pl.nb[l] * NT * PW * PW;
-    if (l > 0) {
-      pl.off_x[l] = off; off += batch * pl.m[l] * n;    // stacked R factors (input of level l)
-      pl.off_out[l] = off; off += batch * pl.m[l] * n;  // Q slab of level l (m_l x kcols, kcols <= n)
-    }
-  }
-  pl.off_flag = off; off += align_up(batch, 64);
-  pl.total = off;
-  return pl;
-}
-
-// The batch is a grid dimension (<= 65535): larger batches are processed in slices of kMaxBatchSlice items, each with its
-// own plan; the slices' workspaces follow each other, so the factor and the apply calls of one (m, n, batch) agree on the
-// layout without any extra state.
-constexpr int64_t kMaxBatchSlice = 65535;
-
-int64_t qr_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t batch) {
-  if (m <= 0 || n <= 0 || batch <= 0) return 0;
-  const int64_t elem = dtype == TTR_F64 ? 8 : 4;
-  int64_t total = 0;
-  for (int64_t b0 = 0; b0 < batch; b0 += kMaxBatchSlice)
-    total += make_plan(m, n, batch - b0 < kMaxBatchSlice ? batch - b0 : kMaxBatchSlice, dtype == TTR_F64).total * elem;
-  return total;
-}
-
-long long* g_qr_dbg = nullptr;  // set through ttr_debug_set_qr_stamps (diagnostics only)
-int g_qr_dbg_bx = 0, g_qr_dbg_by = 0;  // which level-0 block stamps (ttr_debug_set_knob: a block in the middle of the grid shows the
-                                        // steady state -- block (0, 0) starts together with every other first-wave block)
-// ttr_debug_set_knob(TTR_KNOB_QR_PACK): pushed level-0 blocks pack two mode indices per wave when Rm has numerical rank <= 32.
-// 3 (default): blocks b >= nb / 2 are absorbed by b - nb / 2 and the launch is BLOCK-MAJOR (grid (batch, nb)): all working
-// blocks are dispatched first, the absorbed ones (which return after ~12 k cycles) last.  1 / 2 (item-major grid, the working
-// half alternating with the item / even-odd blocks): measured WITHOUT gain -- the dispatcher stalls when long and short
-// workgroups alternate in launch order (level-0 launch 1.78 ms against 1.60 ms unpacked, although the working blocks cost
-// what an unpacked block costs and there are half as many); block-major: 1.1 ms, the metric step 20.9 -> 17.5 ms
-// (tools/probes/qr_pack_stamps.py, profiles/r04_qr_pack_ab.txt).  0 = never pack.
-int g_qr_pack = 3;
-int g_qr_stagger = 0;      // ttr_debug_set_knob(TTR_KNOB_QR_STAGGER): see QrLevel::stagger_kc
-int g_qr_interleave = 1;   // ttr_debug_set_knob(TTR_KNOB_QR_INTERLEAVE): see block_of (0 = round 4's block-major order, A/B)
-int g_rank_skip_c = 8;   // ttr_debug_set_knob(TTR_KNOB_QR_RANK_SKIP, c): threshold factor of the rank-revealing early exit (0 = off)
-int g_qr_variant = 1;           // ttr_debug_set_knob(TTR_KNOB_QR_PANEL): 1 = pair steps in the 8-wave blocks (default), 0 = one reflector at a time
-
-struct Pushed {  // level-0 operands of a fused push (nullptr Rm: plain factorisation)
-  const void* Rm = nullptr;
-  int64_t ldrm = 0, strideRm = 0;
-  const void* Cn = nullptr;
-  int64_t strideCn = 0;
-  const void* Cn2 = nullptr;  // block-diagonal core: second block
-  int64_t strideCn2 = 0;
-  int sumRa = 0, sumCa = 0;
-  int k = 0, Rin = 0, I = 0;
-  int32_t* expo_acc = nullptr;  // QrLevel::expo_acc of the top level (plain factorisations too)
-};
-
+// ---------------------------------------------------------------- the two small kernels around a pushed level 0
 // R <- R 2^-e in place, e = exponent of the item's largest entry, expo_acc[item] += e: the top level of a PUSHED factorisation
 // that has a single level (a handful of mode indices: never the hot path) -- see QrLevel::expo_acc
 template <typename T>
@@ -2018,108 +1800,260 @@ __global__ __launch_bounds__(512) void pack_flags_kernel(const T* __restrict__ R
   }
 }
 
-int g_qr_l1_idle = 1;     // level 1 of packed items: the absorbed leaves' zero rows are skipped by the factor kernel (QrLevel::live_half) and by
-                          // the apply kernel (QrApply::half_zero: waves 4 .. 7 idle); 0 with bit 1 of TTR_KNOB_QR_PACK_PRE: ordinary rows (A/B)
-int g_qr_pack_pre_min = 256;   // smallest batch that takes the packing decision ahead of the launch
-int g_qr_pack_pre = 1;   // ttr_debug_set_knob(TTR_KNOB_QR_PACK_PRE): 0 = every block derives the packing decision from Rm itself (round 5)
+// ---------------------------------------------------------------- host-side tree
+// The run-time switches of this unit (ttr_debug_set_knob / ttr_debug_set_qr_stamps; process-wide).  What each value does is described
+// at its TTR_KNOB_* in include/ttround_hip.h, what it measured in profiles/HISTORY.md ("QR knobs: the A/B runs behind them").
+long long* g_qr_dbg = nullptr;          // ttr_debug_set_qr_stamps: cycle stamps of one level-0 block (diagnostics only)
+int g_qr_dbg_bx = 0, g_qr_dbg_by = 0;   // TTR_KNOB_QR_STAMP_BX / _BY: which level-0 block stamps
+int g_qr_variant = 1;      // TTR_KNOB_QR_PANEL: 1 = pair steps in the 8-wave blocks, 0 = one reflector at a time
+int g_qr_f64_nw4 = 0;      // TTR_KNOB_QR_F64_NW4: bit 0 / 1 = fp64 / fp32 trees out of 4-wave blocks only; bit 2 = fp32 matrices of <= 256 rows on 8-wave PAIR blocks
+int g_rank_skip_c = 8;     // TTR_KNOB_QR_RANK_SKIP: threshold factor c of the rank-revealing early exit and of the packing test (0 = off)
+int g_qr_pack = 3;         // TTR_KNOB_QR_PACK: 3 = rank <= 32 items pack two mode indices per wave, block-major launch; 1 / 2 = item-major; 0 = never
+int g_qr_interleave = 1;   // TTR_KNOB_QR_INTERLEAVE: see block_of (0 = all items' block 0, then all items' block 1, ...)
+int g_qr_stagger = 0;      // TTR_KNOB_QR_STAGGER: see QrLevel::stagger_kc
+int g_qr_pack_pre = 1;     // TTR_KNOB_QR_PACK_PRE bit 0: the packing decision is taken ahead of the launch (pack_flags_kernel)
+int g_qr_l1_idle = 1;      // TTR_KNOB_QR_PACK_PRE bit 1, inverted: level 1 of a packed item skips the absorbed leaves' zero rows
+int g_qr_pack_pre_min = 256;   // smallest batch that takes the packing decision ahead of the launch, and level 1 as two launches
+int g_qr_pair4 = 1;        // TTR_KNOB_QR_PAIR4: the FOUR-wave pair instance for bit 0 = level 1 of packed items; bit 1 = plain fp32 first cores (tests' hook)
 
-// Level 1 of a two-level tree above a pushed level 0 whose items may have PACKED their rows (TTR_KNOB_QR_PACK = 3: the leaves
-// b >= nb / 2 of a packed item are absorbed and write a zero R): the per-item leaf flags (workspace, off_flag) tell the level-1
-// factor and apply kernels that rows >= 256 of the item's 512 stacked rows are exactly zero.  One predicate for both sides.
-static bool l1_half_zero(const QrPlan& pl, int l, int n, bool pushed) {
-  return l == 1 && pl.levels == 2 && pushed && g_qr_pack == 3 && g_qr_l1_idle && pl.nb[0] == 8 && pl.nw[1] == 8 && n == 64 && pl.m[1] == 512;
-}
+struct QrPlan {
+  int n;          // columns
+  int64_t batch;  // items (<= kMaxBatchSlice)
+  int levels;
+  int npad;  // 16 * NT
+  int64_t m[16];
+  int nb[16];
+  int nw[16];  // waves per block on this level (block rows = 64 * nw)
+  // workspace offsets in elements
+  int64_t off_vt[16], off_tau[16], off_tg[16], off_x[16], off_out[16];
+  int64_t off_flag;  // one int32 per item (stored in an element slot): level-0 row packing of a pushed factorisation
+  int64_t total;  // elements
+};
 
-// A plain (not pushed) level on the 8-wave pair kernel: the instance for `nlq` live quarters of the 512-row block (1 .. 4)
-template <typename T, int NT>
-static void factor_launch(int nlq, dim3 grid, hipStream_t stream, const QrLevel<T>& p) {
-  if (nlq >= 4) hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 8>), grid, dim3(512), 0, stream, p);
-  else if (nlq == 3) hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 6>), grid, dim3(512), 0, stream, p);
-  else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 4>), grid, dim3(512), 0, stream, p);
-}
+static int nt_for(int64_t n) { return n <= 16 ? 1 : (n <= 32 ? 2 : 4); }
+static bool nw4_forced(bool f64) { return f64 ? (g_qr_f64_nw4 & 1) != 0 : (g_qr_f64_nw4 & 2) != 0; }
+static int nw_for(int64_t rows, bool f64) { return ((rows > BR4 || (!f64 && (g_qr_f64_nw4 & 4) != 0)) && !nw4_forced(f64)) ? 8 : 4; }
 
-// ttr_debug_set_knob(TTR_KNOB_QR_PAIR4).  Bit 0 (default): level 1 of the packed items of a launch (QrLevel::live_half) runs on the
-// FOUR-wave pair instance -- the 256 live rows as a 256-thread block, four blocks and so four panel chains per CU where the 8-wave
-// NQL = 4 instance has two; bit-identical.  Bit 1: plain fp32 matrices of <= 256 rows and more than 32 columns as well (rank-revealing
-// pair steps instead of the single-step kernel: the last bits of R differ; the tests' hook, and the first core's A/B).
-int g_qr_pair4 = 1;
-
-// The four-wave pair instance (fp32, 64 columns) over `grid` in 256-thread blocks, writing reflector columns of `vt_rows` rows;
-// false when `want` is off or the instance does not exist for <T, NT>: the caller launches what it launched before.
-template <typename T, int NT>
-static bool pair4_launch(bool want, int vt_rows, dim3 grid, hipStream_t stream, QrLevel<T> p) {
-  if constexpr (sizeof(T) == 4 && NT == 4) {
-    if (!want) return false;
-    p.vt_rows = vt_rows;
-    hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, true>), grid, dim3(256), 0, stream, p);
-    return true;
+static QrPlan make_plan(int64_t m, int64_t n, int64_t batch, bool f64) {
+  QrPlan pl{};
+  pl.n = (int)n; pl.batch = batch;
+  const int NT = nt_for(n);
+  pl.npad = NT * PW;
+  int64_t cur = m;
+  int L = 0;
+  for (;;) {
+    pl.m[L] = cur;
+    pl.nw[L] = nw_for(cur, f64);
+    pl.nb[L] = (int)ceil_div(cur, 64 * pl.nw[L]);
+    ++L;
+    if (pl.nb[L - 1] <= 1) break;
+    cur = (int64_t)pl.nb[L - 1] * n;
   }
-  return false;
+  pl.levels = L;
+  int64_t off = 0;
+  for (int l = 0; l < L; ++l) {
+    pl.off_vt[l] = off; off += batch * pl.nb[l] * pl.npad * 64 * pl.nw[l];
+    pl.off_tau[l] = off; off += align_up(batch * pl.nb[l] * pl.npad, 64);
+    pl.off_tg[l] = off; off += batch * pl.nb[l] * NT * PW * PW;
+    if (l > 0) {
+      pl.off_x[l] = off; off += batch * pl.m[l] * n;    // stacked R factors (input of level l)
+      pl.off_out[l] = off; off += batch * pl.m[l] * n;  // Q slab of level l (m_l x kcols, kcols <= n)
+    }
+  }
+  pl.off_flag = off; off += align_up(batch, 64);
+  pl.total = off;
+  return pl;
+}
+
+// The batch is a grid dimension (<= 65535): larger batches are processed in slices of kMaxBatchSlice items, each with its
+// own plan; the slices' workspaces follow each other, so the factor and the apply calls of one (m, n, batch) agree on the
+// layout without any extra state.
+constexpr int64_t kMaxBatchSlice = 65535;
+
+struct Dims { int64_t m, n, batch; };   // rows, columns and items of a call
+// One slice of a call's batch: its first item, its own plan (plan.batch items), its part of the call's workspace (nullptr: sizing)
+struct Slice { int64_t b0; const QrPlan& plan; void* ws; int64_t ws_bytes; };
+
+// f(slice) for every slice of the batch, in order; stops at the first result that is not TTR_OK and returns it.  With a workspace,
+// no slice runs unless the whole call fits: one slice is checked by its own plan (the usual call plans once), a sliced batch first.
+template <typename F>
+static int for_each_slice(const Dims& d, bool f64, void* ws, int64_t ws_bytes, F&& f) {
+  const int64_t whole = (ws && d.batch > kMaxBatchSlice) ? qr_workspace_bytes(f64 ? TTR_F64 : TTR_F32, d.m, d.n, d.batch) : 0;
+  TTR_REQUIRE(ws_bytes >= whole, TTR_E_WORKSPACE, "ttr_qr: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)whole);
+  int64_t off = 0;
+  for (int64_t b0 = 0; b0 < d.batch; b0 += kMaxBatchSlice) {
+    const QrPlan pl = make_plan(d.m, d.n, d.batch - b0 < kMaxBatchSlice ? d.batch - b0 : kMaxBatchSlice, f64);
+    const int64_t bytes = pl.total * (f64 ? 8 : 4);
+    TTR_REQUIRE(!ws || off + bytes <= ws_bytes, TTR_E_WORKSPACE, "ttr_qr: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)(off + bytes));
+    const int rc = f(Slice{b0, pl, ws ? (char*)ws + off : nullptr, bytes});
+    if (rc != TTR_OK) return rc;
+    off += bytes;
+  }
+  return TTR_OK;
+}
+
+int64_t qr_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t batch) {
+  if (m <= 0 || n <= 0 || batch <= 0) return 0;
+  int64_t total = 0;
+  for_each_slice({m, n, batch}, dtype == TTR_F64, nullptr, 0, [&](const Slice& s) { total += s.ws_bytes; return TTR_OK; });
+  return total;
+}
+
+// A batch of matrices: element (row, col) of item b at p[b * stride + row * ld + col * cs]
+template <typename T>
+struct Mat {
+  T* p;
+  int64_t ld, stride, cs = 1;
+  Mat from(int64_t b0) const { return {p ? p + b0 * stride : nullptr, ld, stride, cs}; }   // items b0 ..
+};
+
+struct Pushed {  // level-0 operands of a fused push (nullptr Rm: plain factorisation)
+  const void* Rm = nullptr;
+  int64_t ldrm = 0, strideRm = 0;
+  const void* Cn = nullptr;
+  int64_t strideCn = 0;
+  const void* Cn2 = nullptr;  // block-diagonal core: second block
+  int64_t strideCn2 = 0;
+  int sumRa = 0, sumCa = 0;
+  int k = 0, Rin = 0, I = 0;
+  int32_t* expo_acc = nullptr;  // QrLevel::expo_acc of the top level (plain factorisations too)
+};
+
+template <typename T>
+static Pushed pushed_from(Pushed pu, int64_t b0) {   // the operands of items b0 ..
+  if (pu.Rm) pu.Rm = (const T*)pu.Rm + b0 * pu.strideRm;
+  if (pu.Cn) pu.Cn = (const T*)pu.Cn + b0 * pu.strideCn;
+  if (pu.Cn2) pu.Cn2 = (const T*)pu.Cn2 + b0 * pu.strideCn2;
+  if (pu.expo_acc) pu.expo_acc += b0;
+  return pu;
+}
+
+struct ApplyPushed {  // what the apply of a pushed factorisation adds at level 0 (k = 0: plain factorisation)
+  int k = 0, I = 0;
+  void* G = nullptr;        // QrApply::Gp, the fused row Gram partials: [batch][nb0][64][64]
+  int skip_zero_rows = 0;   // QrApply::skip_zero_rows
+};
+
+// f(IC<1>{}), f(IC<2>{}) or f(IC<4>{}): the 16-column tiles that hold `cols` columns (NT for n, NTC for kcols); f(float{}) or f(double{})
+template <typename F>
+static int with_nt(int64_t cols, F&& f) { return cols <= 16 ? f(IC<1>{}) : cols <= 32 ? f(IC<2>{}) : f(IC<4>{}); }
+template <typename F>
+static int with_type(int dtype, F&& f) { return dtype == TTR_F32 ? f(float{}) : f(double{}); }
+
+// The launch shape of level l, and what the factor and the apply side of one factorisation have to agree on.
+struct LevelGeom {
+  int grid_swap;    // QrLevel / QrApply::grid_swap: the block order (block_of)
+  dim3 grid;        // (nb, batch), or (batch, nb) with grid_swap
+  int nlq;          // live quarters of the level's longest block (rows beyond a shorter block's are loaded as zeros)
+  bool half_zero;   // QrApply::half_zero: level 1 above a PACKED level 0 -- the leaf flags say that rows >= 256 of the item's 512 are zero
+  bool live_half;   // QrLevel::live_half: half_zero, and the factor side launches the level twice (packed items, then the rest)
+};
+
+// `pushed`: the factorisation is a fused push.  `sum_core`: its core is block-diagonal (ttr_qr_factor_pushed_sum), which never packs.
+// The two sides do NOT pass the same `sum_core`: the factor side launches level 0 of a sum item-major (grid_swap = 0), while
+// ttr_qr_apply_pushed is not told where its factorisation came from, passes false and launches level 0 block-major whenever
+// TTR_KNOB_QR_PACK = 3.  Harmless -- grid_swap is only the order in which a launch visits its (item, block) pairs, and the flags of
+// a sum are all 0 -- but nothing may be derived from "both sides used the same order".
+static LevelGeom level_geom(const QrPlan& pl, int l, bool pushed, bool sum_core) {
+  LevelGeom g;
+  const bool block_major = g_qr_pack == 3 && l == 0 && pushed && !sum_core;
+  g.grid_swap = block_major ? ((g_qr_interleave && (pl.nb[l] & 1) == 0) ? 2 : 1) : 0;
+  g.grid = g.grid_swap ? dim3((unsigned)pl.batch, (unsigned)pl.nb[l]) : dim3((unsigned)pl.nb[l], (unsigned)pl.batch);
+  g.nlq = (int)ceil_div(ceil_div(pl.m[l], (int64_t)pl.nb[l]), (int64_t)16 * pl.nw[l]);
+  // TTR_KNOB_QR_PACK = 3: the leaves b >= nb / 2 of a packed item are absorbed and write a zero R, so half of level 1's rows are zero
+  g.half_zero = l == 1 && pl.levels == 2 && pushed && g_qr_pack == 3 && g_qr_l1_idle && pl.nb[0] == 8 && pl.nw[1] == 8 && pl.n == 64 && pl.m[1] == 512;
+  // (from g_qr_pack_pre_min items on: in a latency-bound small-batch sweep the launch that only returns costs what the shorter chain saves)
+  g.live_half = g.half_zero && g_qr_variant != 0 && pl.batch >= g_qr_pack_pre_min;
+  return g;
+}
+
+// Level 0 of a fused push takes its packing decision AHEAD of the launch (pack_flags_kernel, QrLevel::pack_pre): exactly when the kernel's
+// own `packed` path can be taken at all.  Mirrors the kernel's static conditions: 8-wave PAIR blocks (kFull && NW == 8 && PAIR), whole
+// shapes (all 16 NT columns), k == 64, Rin a multiple of 16 and <= 64, an even number of blocks, I == 8 nb (every mode index valid),
+// ldrm >= Rin; packing on at all (pack_ok, c > 0).  From g_qr_pack_pre_min items on (profiles/HISTORY.md: below, no tail to save).
+static bool push_packs_ahead(const QrPlan& pl, const Pushed& pu, int pack_ok) {
+  return pu.Rm && g_qr_pack_pre && pl.batch >= g_qr_pack_pre_min && pack_ok && g_rank_skip_c > 0 && pl.nw[0] == 8 && g_qr_variant != 0 &&
+         pu.k == 64 && pu.Rin <= 64 && (pu.Rin & 15) == 0 && pl.n == pl.npad && (pl.nb[0] & 1) == 0 && pu.I == 8 * pl.nb[0] && pu.ldrm >= pu.Rin;
+}
+
+// The instances of qr_factor_kernel<T, NT, PUSHED, NW, PAIR, NQL> the host launches (NQL8 / 6 / 4: 4 / 3 / <= 2 live quarters)
+enum class Inst { None, Pushed8Pair, Pushed8Single, Pushed4, Plain8PairNQL8, Plain8PairNQL6, Plain8PairNQL4, Plain8Single, Plain4Pair, Plain4Single };
+struct InstPair { Inst first, second; };   // second != None: the level is launched twice (packed items, then the rest)
+
+// Which instance(s) factor level l.  `has_pair4`: the four-wave pair instance exists for <T, NT> (fp32, 64 columns); where it does
+// not, level 1 of the packed items stays on the 8-wave NQL = 4 instance and the tests' hook on the single-step kernel.
+static InstPair factor_instances(const QrPlan& pl, int l, bool pushed, const LevelGeom& g, bool has_pair4, int variant, int pair4) {
+  const bool pair = variant != 0;
+  if (pl.nw[l] == 8) {
+    if (pushed) return {pair ? Inst::Pushed8Pair : Inst::Pushed8Single, Inst::None};
+    if (!pair) return {Inst::Plain8Single, Inst::None};
+    if (g.live_half) return {(has_pair4 && (pair4 & 1) != 0) ? Inst::Plain4Pair : Inst::Plain8PairNQL4, Inst::Plain8PairNQL8};
+    return {g.nlq >= 4 ? Inst::Plain8PairNQL8 : g.nlq == 3 ? Inst::Plain8PairNQL6 : Inst::Plain8PairNQL4, Inst::None};
+  }
+  if (pushed) return {Inst::Pushed4, Inst::None};
+  return {(has_pair4 && (pair4 & 2) != 0 && pl.levels == 1 && pair) ? Inst::Plain4Pair : Inst::Plain4Single, Inst::None};
 }
 
 template <typename T, int NT>
-static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, int64_t strideA, T* R, int64_t ldr,
-                      int64_t strideR, T* ws, const QrPlan& pl, const Pushed& pu, hipStream_t stream, int64_t a_cs = 1) {
-  const int L = pl.levels;
+static void launch_factor(Inst inst, dim3 grid, hipStream_t stream, const QrLevel<T>& p) {
+  switch (inst) {
+    case Inst::Pushed8Pair: hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, true>), grid, dim3(512), 0, stream, p); break;
+    case Inst::Pushed8Single: hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, false>), grid, dim3(512), 0, stream, p); break;
+    case Inst::Pushed4: hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 4, false>), grid, dim3(256), 0, stream, p); break;
+    case Inst::Plain8PairNQL8: hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 8>), grid, dim3(512), 0, stream, p); break;
+    case Inst::Plain8PairNQL6: hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 6>), grid, dim3(512), 0, stream, p); break;
+    case Inst::Plain8PairNQL4: hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, true, 4>), grid, dim3(512), 0, stream, p); break;
+    case Inst::Plain8Single: hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, false>), grid, dim3(512), 0, stream, p); break;
+    case Inst::Plain4Single: hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, false>), grid, dim3(256), 0, stream, p); break;
+    case Inst::Plain4Pair:   // (only where it exists: factor_instances, has_pair4)
+      if constexpr (sizeof(T) == 4 && NT == 4) hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, true>), grid, dim3(256), 0, stream, p);
+      break;
+    case Inst::None: break;
+  }
+}
+
+template <typename T, int NT>
+static int factor_run(Mat<const T> A, Mat<T> R, T* ws, const QrPlan& pl, const Pushed& pu, hipStream_t stream) {
+  const int L = pl.levels, n = pl.n;
+  const int64_t batch = pl.batch;
   for (int l = 0; l < L; ++l) {
+    const bool pushed = (l == 0 && pu.Rm);
+    const LevelGeom g = level_geom(pl, l, pu.Rm != nullptr, pu.Cn2 != nullptr);
     QrLevel<T> p;
     p.dbg = (l == 0) ? g_qr_dbg : nullptr;
     p.dbg_bx = g_qr_dbg_bx; p.dbg_by = g_qr_dbg_by;
     p.rank_skip_c = g_rank_skip_c;
-    p.pack_flag = (l == 0 && pu.Rm) ? reinterpret_cast<int32_t*>(ws + pl.off_flag) : nullptr;
+    p.pack_flag = pushed ? reinterpret_cast<int32_t*>(ws + pl.off_flag) : nullptr;
     p.pack_ok = (g_qr_pack && pu.Cn2 == nullptr) ? g_qr_pack : 0;
     p.Rm = (const T*)pu.Rm; p.ldrm = pu.ldrm; p.strideRm = pu.strideRm;
     p.Cn = (const T*)pu.Cn; p.strideCn = pu.strideCn; p.pk = pu.k; p.pRin = pu.Rin; p.pI = pu.I;
     p.Cn2 = (const T*)pu.Cn2; p.strideCn2 = pu.strideCn2; p.sumRa = pu.sumRa; p.sumCa = pu.sumCa;
-    p.X = l == 0 ? A : ws + pl.off_x[l];
-    p.ldx = l == 0 ? lda : n;
-    p.xcs = l == 0 ? a_cs : 1;
-    p.strideX = l == 0 ? strideA : pl.m[l] * n;
+    p.X = l == 0 ? A.p : ws + pl.off_x[l];
+    p.ldx = l == 0 ? A.ld : n;
+    p.xcs = l == 0 ? A.cs : 1;
+    p.strideX = l == 0 ? A.stride : pl.m[l] * n;
     p.m = pl.m[l]; p.n = n; p.nb = pl.nb[l];
     p.Vt = ws + pl.off_vt[l];
     p.tau = ws + pl.off_tau[l];
     p.Tg = ws + pl.off_tg[l];
     p.top = (l == L - 1);
-    p.expo_acc = (p.top && !(l == 0 && pu.Rm)) ? pu.expo_acc : nullptr;
+    p.expo_acc = (p.top && !pushed) ? pu.expo_acc : nullptr;
     p.stagger_kc = g_qr_stagger;
-    p.vt_rows = 0;
-    // (from g_qr_pack_pre_min items on, like the packing decision ahead of the launch: the level then costs two launches, one of
-    // which only returns -- in a latency-bound small-batch sweep that launch costs what the shorter chain saves)
-    p.live_half = (l1_half_zero(pl, l, n, pu.Rm != nullptr) && g_qr_variant != 0 && batch >= g_qr_pack_pre_min)
-                      ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
-    if (p.top) { p.Rout = R; p.ldr = ldr; p.strideR = strideR; }
+    p.live_half = g.live_half ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
+    if (p.top) { p.Rout = R.p; p.ldr = R.ld; p.strideR = R.stride; }
     else { p.Rout = ws + pl.off_x[l + 1]; p.ldr = n; p.strideR = pl.m[l + 1] * n; }
-    const bool pushed = (l == 0 && pu.Rm);
-    // the packing decision ahead of the launch: exactly when the kernel's `packed` path can be taken at all (8-wave PAIR blocks, whole
-    // shapes: every mode index valid, all 16 NT columns, Rin a multiple of 16; a 64-row R; an even number of blocks)
-    // (from 256 items on: below, the absorbed blocks of a launch run beside its working blocks -- no tail to save -- and the extra
-    // launch costs a latency-bound small-batch sweep 5 us per core)
-    p.pack_pre = (pushed && g_qr_pack_pre && batch >= g_qr_pack_pre_min && p.pack_ok && p.pack_flag && g_rank_skip_c > 0 && pl.nw[l] == 8 && g_qr_variant != 0 &&
-                  pu.k == 64 && pu.Rin <= 64 && (pu.Rin & 15) == 0 && n == PW * NT && (pl.nb[l] & 1) == 0 && pu.I == 8 * pl.nb[l] &&
-                  pu.ldrm >= pu.Rin) ? 1 : 0;
+    p.pack_pre = (pushed && push_packs_ahead(pl, pu, p.pack_ok)) ? 1 : 0;
+    p.grid_swap = g.grid_swap;
+    const InstPair insts = factor_instances(pl, l, pushed, g, sizeof(T) == 4 && NT == 4, g_qr_variant, g_qr_pair4);
     {
       ProfScope prof(TTR_PROF_QR_FACTOR, stream);
       if (p.pack_pre)
         hipLaunchKernelGGL((pack_flags_kernel<T>), dim3((unsigned)batch), dim3(512), 0, stream, (const T*)pu.Rm, pu.ldrm,
                            pu.strideRm, pu.Rin, batch, g_rank_skip_c, p.pack_ok, p.pack_flag);
-      p.grid_swap = (p.pack_ok == 3 && l == 0 && pu.Rm) ? ((g_qr_interleave && (pl.nb[l] & 1) == 0) ? 2 : 1) : 0;
-      const dim3 grid = p.grid_swap ? dim3((unsigned)batch, (unsigned)pl.nb[l]) : dim3((unsigned)pl.nb[l], (unsigned)batch);
-      // live quarters of this level's blocks (the longest block: rows beyond a shorter one's are loaded as zeros)
-      const int64_t rows_max = ceil_div(pl.m[l], (int64_t)pl.nb[l]);
-      const int nlq = (int)ceil_div(rows_max, (int64_t)16 * pl.nw[l]);
-      if (pl.nw[l] == 8 && g_qr_variant != 0) {
-        if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, true>), grid, dim3(512), 0, stream, p);
-        else if (p.live_half) {   // packed items, then the rest
-          if (!pair4_launch<T, NT>((g_qr_pair4 & 1) != 0, 64 * pl.nw[l], grid, stream, p)) factor_launch<T, NT>(2, grid, stream, p);
-          factor_launch<T, NT>(4, grid, stream, p);
-        } else factor_launch<T, NT>(nlq, grid, stream, p);
-      } else if (pl.nw[l] == 8) {
-        if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 8, false>), grid, dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 8, false>), grid, dim3(512), 0, stream, p);
-      } else {
-        if (pushed) hipLaunchKernelGGL((qr_factor_kernel<T, NT, true, 4, false>), grid, dim3(256), 0, stream, p);
-        else if (!pair4_launch<T, NT>((g_qr_pair4 & 2) != 0 && L == 1 && g_qr_variant != 0, 256, grid, stream, p))   // (the test hook)
-          hipLaunchKernelGGL((qr_factor_kernel<T, NT, false, 4, false>), grid, dim3(256), 0, stream, p);
+      for (const Inst inst : {insts.first, insts.second}) {
+        // (the four-wave pair block writes reflector columns of the LEVEL's block rows: zeros below its own 256, QrLevel::vt_rows)
+        p.vt_rows = inst == Inst::Plain4Pair ? 64 * pl.nw[l] : 0;
+        launch_factor<T, NT>(inst, g.grid, stream, p);
       }
     }
     if (work_census_on()) {   // what this launch executed, from the taus / flags it left behind (outside the timed scope)
@@ -2142,7 +2076,7 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
     if constexpr (sizeof(T) == 4) {
       const int64_t mt = (int64_t)pu.k * pu.I;
       ProfScope prof(TTR_PROF_QR_FACTOR, stream);
-      hipLaunchKernelGGL(r_expo_kernel<T>, dim3((unsigned)batch), dim3(256), 0, stream, R, (int)(mt < n ? mt : n), n, ldr, strideR,
+      hipLaunchKernelGGL(r_expo_kernel<T>, dim3((unsigned)batch), dim3(256), 0, stream, R.p, (int)(mt < n ? mt : n), n, R.ld, R.stride,
                          pu.expo_acc);
     }
   }
@@ -2151,33 +2085,32 @@ static int factor_run(int64_t m, int n, int64_t batch, const T* A, int64_t lda, 
 }
 
 template <typename T, int NT, int NTC>
-static int apply_run(int64_t m, int n, int64_t batch, const T* ws, T* wsw, const QrPlan& pl, const T* C, int64_t ldc,
-                     int64_t strideC, int kc, T* Out, int64_t ldo, int64_t strideO, int pk, int pI, T* Gp, hipStream_t stream,
-                     int64_t o_cs = 1, int skipz = 0) {
-  const int L = pl.levels;
+static int apply_run(T* ws, const QrPlan& pl, Mat<const T> C, int kc, Mat<T> Out, const ApplyPushed& ap, hipStream_t stream) {
+  const int L = pl.levels, n = pl.n;
+  const int64_t batch = pl.batch;
   for (int l = L - 1; l >= 0; --l) {
+    const LevelGeom g = level_geom(pl, l, ap.k > 0, false);   // (false: see level_geom)
     QrApply<T> p;
-    p.ocs = l == 0 ? o_cs : 1;
+    p.ocs = l == 0 ? Out.cs : 1;
     p.Vt = ws + pl.off_vt[l];
     p.tau = ws + pl.off_tau[l];
     p.Tg = ws + pl.off_tg[l];
     p.m = pl.m[l]; p.n = n; p.nb = pl.nb[l]; p.kcols = kc;
-    if (l == L - 1) { p.Top = C; p.ldtop = ldc; p.strideTop = strideC; }  // C == nullptr: identity
+    if (l == L - 1) { p.Top = C.p; p.ldtop = C.ld; p.strideTop = C.stride; }  // C.p == nullptr: identity
     else { p.Top = ws + pl.off_out[l + 1]; p.ldtop = kc; p.strideTop = pl.m[l + 1] * n; }
-    if (l == 0) { p.Out = Out; p.ldout = ldo; p.strideOut = strideO; }
-    else { p.Out = wsw + pl.off_out[l]; p.ldout = kc; p.strideOut = pl.m[l] * n; }
-    p.pk = (l == 0) ? pk : 0; p.pI = (l == 0) ? pI : 0;
-    p.Gp = (l == 0) ? Gp : nullptr;
-    p.pack_flag = (l == 0 && pk > 0) ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
-    p.half_zero = l1_half_zero(pl, l, n, pk > 0) ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
-    p.skip_zero_rows = (l == 0) ? skipz : 0;
+    if (l == 0) { p.Out = Out.p; p.ldout = Out.ld; p.strideOut = Out.stride; }
+    else { p.Out = ws + pl.off_out[l]; p.ldout = kc; p.strideOut = pl.m[l] * n; }
+    p.pk = (l == 0) ? ap.k : 0; p.pI = (l == 0) ? ap.I : 0;
+    p.Gp = (l == 0) ? (T*)ap.G : nullptr;
+    p.pack_flag = (l == 0 && ap.k > 0) ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
+    p.half_zero = g.half_zero ? reinterpret_cast<const int32_t*>(ws + pl.off_flag) : nullptr;
+    p.skip_zero_rows = (l == 0) ? ap.skip_zero_rows : 0;
     p.dbg = (l == 0) ? g_qr_dbg : nullptr;
+    p.grid_swap = g.grid_swap;
     {
       ProfScope prof(TTR_PROF_QR_APPLY, stream);
-      p.grid_swap = (g_qr_pack == 3 && p.pack_flag) ? ((g_qr_interleave && (pl.nb[l] & 1) == 0) ? 2 : 1) : 0;
-      const dim3 grid = p.grid_swap ? dim3((unsigned)batch, (unsigned)pl.nb[l]) : dim3((unsigned)pl.nb[l], (unsigned)batch);
-      if (pl.nw[l] == 8) hipLaunchKernelGGL((qr_apply_kernel<T, NT, NTC, 8>), grid, dim3(512), 0, stream, p);
-      else hipLaunchKernelGGL((qr_apply_kernel<T, NT, NTC, 4>), grid, dim3(256), 0, stream, p);
+      if (pl.nw[l] == 8) hipLaunchKernelGGL((qr_apply_kernel<T, NT, NTC, 8>), g.grid, dim3(512), 0, stream, p);
+      else hipLaunchKernelGGL((qr_apply_kernel<T, NT, NTC, 4>), g.grid, dim3(256), 0, stream, p);
     }
     if (work_census_on())
       work_qr_taus(TTR_PROF_QR_APPLY, p.tau, sizeof(T) == 8, batch * pl.nb[l], pl.nb[l], pl.npad, pl.m[l], 64 * pl.nw[l], n, kc, false, stream);
@@ -2187,75 +2120,26 @@ static int apply_run(int64_t m, int n, int64_t batch, const T* ws, T* wsw, const
 }
 
 template <typename T>
-static int factor_typed(int64_t m, int64_t n, int64_t batch, const void* A, int64_t lda, int64_t strideA, void* R,
-                        int64_t ldr, int64_t strideR, void* ws, int64_t ws_bytes, const Pushed& pu, hipStream_t stream,
-                        int64_t a_cs = 1) {
-  if (batch > kMaxBatchSlice) {  // slices of the batch, one after the other (see qr_workspace_bytes)
-    TTR_REQUIRE(ws_bytes >= qr_workspace_bytes(sizeof(T) == 8 ? TTR_F64 : TTR_F32, m, n, batch), TTR_E_WORKSPACE,
-                "ttr_qr: workspace too small for batch %lld", (long long)batch);
-    char* wsp = (char*)ws;
-    for (int64_t b0 = 0; b0 < batch; b0 += kMaxBatchSlice) {
-      const int64_t nb = batch - b0 < kMaxBatchSlice ? batch - b0 : kMaxBatchSlice;
-      const int64_t wsb = make_plan(m, n, nb, sizeof(T) == 8).total * (int64_t)sizeof(T);
-      Pushed ps = pu;
-      if (ps.Rm) ps.Rm = (const T*)ps.Rm + b0 * ps.strideRm;
-      if (ps.Cn) ps.Cn = (const T*)ps.Cn + b0 * ps.strideCn;
-      if (ps.Cn2) ps.Cn2 = (const T*)ps.Cn2 + b0 * ps.strideCn2;
-      if (ps.expo_acc) ps.expo_acc += b0;
-      const int rc = factor_typed<T>(m, n, nb, A ? (const void*)((const T*)A + b0 * strideA) : nullptr, lda, strideA,
-                                     (T*)R + b0 * strideR, ldr, strideR, wsp, wsb, ps, stream, a_cs);
-      if (rc != TTR_OK) return rc;
-      wsp += wsb;
-    }
-    return TTR_OK;
-  }
-  const QrPlan pl = make_plan(m, n, batch, sizeof(T) == 8);
-  TTR_REQUIRE(ws_bytes >= pl.total * (int64_t)sizeof(T), TTR_E_WORKSPACE, "ttr_qr: workspace %lld < %lld bytes",
-              (long long)ws_bytes, (long long)(pl.total * (int64_t)sizeof(T)));
-  switch (nt_for(n)) {
-    case 1: return factor_run<T, 1>(m, (int)n, batch, (const T*)A, lda, strideA, (T*)R, ldr, strideR, (T*)ws, pl, pu, stream, a_cs);
-    case 2: return factor_run<T, 2>(m, (int)n, batch, (const T*)A, lda, strideA, (T*)R, ldr, strideR, (T*)ws, pl, pu, stream, a_cs);
-    default: return factor_run<T, 4>(m, (int)n, batch, (const T*)A, lda, strideA, (T*)R, ldr, strideR, (T*)ws, pl, pu, stream, a_cs);
-  }
-}
-
-template <typename T, int NT>
-static int apply_nt(int64_t m, int n, int64_t batch, T* ws, const QrPlan& pl, const T* C, int64_t ldc, int64_t strideC,
-                    int kc, T* Out, int64_t ldo, int64_t strideO, int pk, int pI, T* Gp, hipStream_t stream, int64_t o_cs, int skipz) {
-  if (kc <= 16) return apply_run<T, NT, 1>(m, n, batch, ws, ws, pl, C, ldc, strideC, kc, Out, ldo, strideO, pk, pI, Gp, stream, o_cs, skipz);
-  if (kc <= 32) return apply_run<T, NT, 2>(m, n, batch, ws, ws, pl, C, ldc, strideC, kc, Out, ldo, strideO, pk, pI, Gp, stream, o_cs, skipz);
-  return apply_run<T, NT, 4>(m, n, batch, ws, ws, pl, C, ldc, strideC, kc, Out, ldo, strideO, pk, pI, Gp, stream, o_cs, skipz);
+static int factor_typed(const Dims& d, Mat<const T> A, Mat<T> R, void* ws, int64_t ws_bytes, const Pushed& pu, hipStream_t stream) {
+  return for_each_slice(d, sizeof(T) == 8, ws, ws_bytes, [&](const Slice& s) {
+    return with_nt(d.n, [&](auto NT) {
+      return factor_run<T, decltype(NT)::value>(A.from(s.b0), R.from(s.b0), (T*)s.ws, s.plan, pushed_from<T>(pu, s.b0), stream);
+    });
+  });
 }
 
 template <typename T>
-static int apply_typed(int64_t m, int64_t n, int64_t batch, void* ws, int64_t ws_bytes, const void* C, int64_t ldc,
-                       int64_t strideC, int64_t kc, void* Out, int64_t ldo, int64_t strideO, int pk, int pI, void* Gp,
-                       hipStream_t stream, int64_t o_cs = 1, int skipz = 0) {
-  if (batch > kMaxBatchSlice) {
-    TTR_REQUIRE(ws_bytes >= qr_workspace_bytes(sizeof(T) == 8 ? TTR_F64 : TTR_F32, m, n, batch), TTR_E_WORKSPACE,
-                "ttr_qr_apply: workspace too small for batch %lld", (long long)batch);
-    char* wsp = (char*)ws;
-    for (int64_t b0 = 0; b0 < batch; b0 += kMaxBatchSlice) {
-      const int64_t nb = batch - b0 < kMaxBatchSlice ? batch - b0 : kMaxBatchSlice;
-      const int64_t wsb = make_plan(m, n, nb, sizeof(T) == 8).total * (int64_t)sizeof(T);
-      const int rc = apply_typed<T>(m, n, nb, wsp, wsb, C ? (const void*)((const T*)C + b0 * strideC) : nullptr, ldc, strideC, kc,
-                                    (T*)Out + b0 * strideO, ldo, strideO, pk, pI,
-                                    Gp ? (void*)((T*)Gp + b0 * make_plan(m, n, nb, sizeof(T) == 8).nb[0] * (int64_t)(64 * 64)) : nullptr, stream, o_cs, skipz);
-      if (rc != TTR_OK) return rc;
-      wsp += wsb;
-    }
-    return TTR_OK;
-  }
-  const QrPlan pl = make_plan(m, n, batch, sizeof(T) == 8);
-  TTR_REQUIRE(ws_bytes >= pl.total * (int64_t)sizeof(T), TTR_E_WORKSPACE, "ttr_qr_apply: workspace %lld < %lld bytes",
-              (long long)ws_bytes, (long long)(pl.total * (int64_t)sizeof(T)));
-  TTR_REQUIRE(kc >= 1 && kc <= 64 && kc <= n, TTR_E_UNSUPPORTED, "ttr_qr_apply: kcols = %lld outside [1, min(n, 64)]",
+static int apply_typed(const Dims& d, void* ws, int64_t ws_bytes, Mat<const T> C, int64_t kc, Mat<T> Out, const ApplyPushed& ap,
+                       hipStream_t stream) {
+  TTR_REQUIRE(kc >= 1 && kc <= 64 && kc <= d.n, TTR_E_UNSUPPORTED, "ttr_qr_apply: kcols = %lld outside [1, min(n, 64)]",
               (long long)kc);
-  switch (nt_for(n)) {
-    case 1: return apply_nt<T, 1>(m, (int)n, batch, (T*)ws, pl, (const T*)C, ldc, strideC, (int)kc, (T*)Out, ldo, strideO, pk, pI, (T*)Gp, stream, o_cs, skipz);
-    case 2: return apply_nt<T, 2>(m, (int)n, batch, (T*)ws, pl, (const T*)C, ldc, strideC, (int)kc, (T*)Out, ldo, strideO, pk, pI, (T*)Gp, stream, o_cs, skipz);
-    default: return apply_nt<T, 4>(m, (int)n, batch, (T*)ws, pl, (const T*)C, ldc, strideC, (int)kc, (T*)Out, ldo, strideO, pk, pI, (T*)Gp, stream, o_cs, skipz);
-  }
+  return for_each_slice(d, sizeof(T) == 8, ws, ws_bytes, [&](const Slice& s) {
+    ApplyPushed aps = ap;   // (the slice's Gram partials: [nb0][64][64] per item)
+    if (aps.G) aps.G = (T*)aps.G + s.b0 * s.plan.nb[0] * (int64_t)(64 * 64);
+    return with_nt(d.n, [&](auto NT) { return with_nt(kc, [&](auto NTC) {
+      return apply_run<T, decltype(NT)::value, decltype(NTC)::value>((T*)s.ws, s.plan, C.from(s.b0), (int)kc, Out.from(s.b0), aps, stream);
+    }); });
+  });
 }
 
 int qr_max_cols(int) { return 64; }
@@ -2268,8 +2152,10 @@ int qr_factor_dispatch(int dtype, int64_t m, int64_t n, int64_t batch, const voi
   TTR_REQUIRE(!expo_acc || dtype == TTR_F32, TTR_E_UNSUPPORTED, "ttr_qr_factor: expo_acc is an fp32 facility");
   Pushed none;
   none.expo_acc = expo_acc;
-  if (dtype == TTR_F32) return factor_typed<float>(m, n, batch, A, lda, strideA, R, ldr, strideR, ws, ws_bytes, none, stream, a_cs);
-  return factor_typed<double>(m, n, batch, A, lda, strideA, R, ldr, strideR, ws, ws_bytes, none, stream, a_cs);
+  return with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    return factor_typed<T>({m, n, batch}, {(const T*)A, lda, strideA, a_cs}, {(T*)R, ldr, strideR}, ws, ws_bytes, none, stream);
+  });
 }
 
 int qr_apply_dispatch(int dtype, int64_t m, int64_t n, int64_t batch, void* ws, int64_t ws_bytes, const void* C,
@@ -2277,8 +2163,10 @@ int qr_apply_dispatch(int dtype, int64_t m, int64_t n, int64_t batch, void* ws, 
                       hipStream_t stream, int64_t o_cs) {
   TTR_REQUIRE(n <= qr_max_cols(dtype), TTR_E_UNSUPPORTED, "ttr_qr_apply: n = %lld exceeds the %d-column panel kernel",
               (long long)n, qr_max_cols(dtype));
-  if (dtype == TTR_F32) return apply_typed<float>(m, n, batch, ws, ws_bytes, C, ldc, strideC, kc, Out, ldo, strideO, 0, 0, nullptr, stream, o_cs);
-  return apply_typed<double>(m, n, batch, ws, ws_bytes, C, ldc, strideC, kc, Out, ldo, strideO, 0, 0, nullptr, stream, o_cs);
+  return with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    return apply_typed<T>({m, n, batch}, ws, ws_bytes, {(const T*)C, ldc, strideC}, kc, {(T*)Out, ldo, strideO, o_cs}, {}, stream);
+  });
 }
 
 // Pushed variants: the factored matrix is the (k*I) x n left unfolding of Rm * C; level 0 has ceil(I/NW)
@@ -2320,9 +2208,10 @@ int qr_factor_pushed_dispatch(int dtype, int64_t k, int64_t Rin, int64_t I, int6
   pu.Rm = Rm; pu.ldrm = ldrm; pu.strideRm = strideRm; pu.Cn = Cn; pu.strideCn = strideCn;
   pu.k = (int)k; pu.Rin = (int)Rin; pu.I = (int)I;
   pu.expo_acc = expo_acc;
-  const int64_t m = pushed_rows(I, dtype);
-  if (dtype == TTR_F32) return factor_typed<float>(m, n, batch, nullptr, 0, 0, R, ldr, strideR, ws, ws_bytes, pu, stream);
-  return factor_typed<double>(m, n, batch, nullptr, 0, 0, R, ldr, strideR, ws, ws_bytes, pu, stream);
+  return with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    return factor_typed<T>({pushed_rows(I, dtype), n, batch}, {nullptr, 0, 0}, {(T*)R, ldr, strideR}, ws, ws_bytes, pu, stream);
+  });
 }
 
 // Fused push of a block-diagonal core: QR of the left unfolding of Rm * blockdiag(a, b) (a: [ra][I][ca], b: [rb][I][cb]).
@@ -2338,9 +2227,10 @@ int qr_factor_pushed_sum_dispatch(int dtype, int64_t k, int64_t I, int64_t batch
   pu.Rm = Rm; pu.ldrm = ldrm; pu.strideRm = strideRm; pu.Cn = Ca; pu.strideCn = strideCa;
   pu.Cn2 = Cb; pu.strideCn2 = strideCb; pu.sumRa = (int)ra; pu.sumCa = (int)ca;
   pu.k = (int)k; pu.Rin = (int)Rin; pu.I = (int)I;
-  const int64_t m = pushed_rows(I, dtype);
-  if (dtype == TTR_F32) return factor_typed<float>(m, n, batch, nullptr, 0, 0, R, ldr, strideR, ws, ws_bytes, pu, stream);
-  return factor_typed<double>(m, n, batch, nullptr, 0, 0, R, ldr, strideR, ws, ws_bytes, pu, stream);
+  return with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    return factor_typed<T>({pushed_rows(I, dtype), n, batch}, {nullptr, 0, 0}, {(T*)R, ldr, strideR}, ws, ws_bytes, pu, stream);
+  });
 }
 
 // Number of row-Gram partials ttr_qr_apply_pushed_gram writes per batch item (0: the fused Gram epilogue does not cover this shape)
@@ -2362,10 +2252,12 @@ int qr_apply_pushed_dispatch(int dtype, int64_t k, int64_t I, int64_t n, int64_t
   TTR_REQUIRE(!G || g_qr_pack == 0, TTR_E_UNSUPPORTED,
               "ttr_qr_apply_pushed_gram: row packing is enabled (TTR_KNOB_QR_PACK = %d); the fused Gram epilogue needs it off "
               "for the factorisation AND the apply", g_qr_pack);
-  const int64_t m = pushed_rows(I, dtype);
-  if (dtype == TTR_F32)
-    return apply_typed<float>(m, n, batch, ws, ws_bytes, C, ldc, strideC, kc, Out, ldo, strideO, (int)k, (int)I, G, stream, 1, skip_zero_rows);
-  return apply_typed<double>(m, n, batch, ws, ws_bytes, C, ldc, strideC, kc, Out, ldo, strideO, (int)k, (int)I, nullptr, stream, 1, skip_zero_rows);
+  const ApplyPushed ap{(int)k, (int)I, dtype == TTR_F32 ? G : nullptr, skip_zero_rows};   // (the Gram epilogue is fp32 only)
+  return with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    return apply_typed<T>({pushed_rows(I, dtype), n, batch}, ws, ws_bytes, {(const T*)C, ldc, strideC}, kc, {(T*)Out, ldo, strideO}, ap,
+                          stream);
+  });
 }
 
 }  // namespace ttr

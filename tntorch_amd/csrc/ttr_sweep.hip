@@ -299,8 +299,6 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_ke
   T* __restrict__ Ro = p.right + b * p.strideR;
   const bool al2 = ((p.ldm & 1) == 0) && ((p.ldr & 1) == 0) && ((reinterpret_cast<uintptr_t>(Mp) & (2 * sizeof(T) - 1)) == 0) &&
                    ((reinterpret_cast<uintptr_t>(Ro) & (2 * sizeof(T) - 1)) == 0);
-  const bool al4 = ((p.ldm & 3) == 0) && ((p.ldr & 3) == 0) && ((reinterpret_cast<uintptr_t>(Mp) & (4 * sizeof(T) - 1)) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(Ro) & (4 * sizeof(T) - 1)) == 0);
   const int Rl = (p.rows32 && p.rows32[b] != 0 && R > 32) ? 32 : R;   // (see rotgram_kernel: zero rows are not loaded)
   // Step order: every item's rows lie ldm elements apart (8 KB at the metric's bonds) and every item is aligned alike, so
   // workgroups that walk their columns in step would keep hitting the same HBM channels (address bits 8 .. 12 are the column's;
@@ -311,7 +309,7 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_ke
   // a * 0 to their accumulators: bit-identical
   auto main_loop = [&](auto NKC, auto SLC) {
     constexpr int NK = decltype(NKC)::value, SL = decltype(SLC)::value;
-    const bool al = SL == 4 ? al4 : al2;
+    const bool al = al2;
     // the split (nsplit: pick_split) is defined on 32-column chunks; a wave's steps walk its share SL * 16 columns at a time
     int64_t cb, ce;
     split_range((p.n + 31) / 32, p.nsplit, split, cb, ce);
@@ -368,22 +366,15 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_ke
     }
   };
   using I2 = std::integral_constant<int, 2>;
-  using I4 = std::integral_constant<int, 4>;
   using I8 = std::integral_constant<int, 8>;
   using I16 = std::integral_constant<int, 16>;
-  // SL = 4 (16-byte accesses) is compiled only with -DTTR_PROJECT_WIDE: measured SLOWER on the kind (3.14 against 2.96 - 3.01 ms per
-  // 4096-train step, profiles/r06_project_ab.txt; review item 4's wide accesses), and 16 K steps x 4 slabs spill under the
-  // 128-register cap of four workgroups per CU
+  // SL = 4 (16-byte accesses, four interleaved slabs) measured SLOWER and is no longer built: profiles/HISTORY.md, "Retired
+  // compile-time variants"
   if (Rl <= 32) {
-#ifdef TTR_PROJECT_WIDE
-    if (al4) main_loop(I8{}, I4{});
-    else
-#endif
-      main_loop(I8{}, I2{});
+    main_loop(I8{}, I2{});
   } else {
     main_loop(I16{}, I2{});
   }
-  (void)al4;
 }
 
 // ---------------------------------------------------------------- lean builds for `rows32` items (fp32 launches, R = 64)
