@@ -57,7 +57,8 @@ extern "C" {
    symbols fails at load, in the binding and in build()); so were ttr_gather_grad, ttr_gather_grad_workspace_bytes and
    ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
    ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose, and ttr_env_half_apply, and ttr_ritz_parts, ttr_ritz_workspace_bytes, ttr_ritz_gram and
-   ttr_ritz_update.  ttr_version() returns the value the library was built with; the Python
+   ttr_ritz_update, and ttr_ttm_lookup_grad_core_slab_rows, ttr_ttm_lookup_grad_core_workspace_bytes, ttr_ttm_lookup_grad_core,
+   ttr_ttm_lookup_grad_input_workspace_bytes, ttr_ttm_lookup_grad_input and ttr_segment_sum.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1246,6 +1247,68 @@ int64_t ttr_ttm_lookup_workspace_bytes(int64_t P, int64_t I);
 int ttr_ttm_lookup_step(int dtype, int64_t P, int64_t rows_x, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S,
                         const void* X, const void* xrow, const void* G, const int64_t* g_strides, const void* idx,
                         int64_t stride_idx, void* Y, void* oob_flag, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * The backward of ttr_ttm_lookup_step and the segmented row sum of the trainable TT embedding (added under ABI 17; embedding.py
+ * `tt_embedding`, `tt_embedding_bag`).  With X [rows_x, D, R], dY [P, D, O, S] and dX [P, D, R] contiguous, dG
+ * [R, I, O, S] contiguous, and `idx`, `xrow`, `stride_idx` and `oob_flag` as in ttr_ttm_lookup_step:
+ *
+ *   ttr_ttm_lookup_grad_core    dG[r, i, o, s] = sum_{p: idx[p] = i} sum_dd X[xrow ? xrow[p] : p, dd, r] * dY[p, dd, o, s]
+ *   ttr_ttm_lookup_grad_input   dX[p, dd, r]   = sum_{o, s} dY[p, dd, o, s] * G[r, idx[p], o, s]
+ *
+ * `perm` is a contiguous int64 device vector of P entries: the sample ids 0 .. P - 1 grouped by wrapped idx (group 0 first; the
+ * order inside a group is the caller's, a stable sort keeps the sample order).  Neither entry sorts: each counts the groups
+ * (histogram and scan on the device, into `workspace`; no readback) and reads its rows through perm.  idx (wrapped), perm and
+ * xrow (not wrapped) are validated on the device first: a bad entry ORs *oob_flag with 1 and then nothing else is written, as when
+ * the word is set on entry; the word is never cleared.  No host synchronisation, no atomics on floating-point data, no rank
+ * limit, 64-bit element offsets; v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 with operands and accumulators in the dtype.
+ *
+ * ttr_ttm_lookup_grad_core: slice i is one GEMM with M = R, N = O S and K = cnt_i D, the K rows gathered D R resp. D N contiguous
+ * elements per sample; a workgroup owns a 64 x 64 tile of (r, n) and one SLAB of the slice's K range, walked in chunks of 32.  The
+ * slab length ttr_ttm_lookup_grad_core_slab_rows(dtype, P, D, R, I, O, S) reads its arguments only: with tiles = ceil(R / 64)
+ * ceil(O S / 64) and want = max(1, 1024 / tiles), slab_rows = max(256, ceil(P D / want) rounded up to a multiple of 32).  Slice i
+ * has ceil(cnt_i D / slab_rows) slabs, numbered by a scan on the device.  A slice of one slab writes dG directly; the slabs of the
+ * others write partial tiles to the workspace, and a second launch adds a slice's partials in increasing slab order (one chain
+ * per element) and writes exact zeros for a slice without samples.  The workspace (ttr_ttm_lookup_grad_core_workspace_bytes)
+ * holds the counts and ceil(P D / slab_rows) + I partial tiles of R x O S, the host-side upper bound of the slab count.  The same
+ * inputs and the same perm give the same bits, and so do xrow = NULL and the identity map, wherever the buffers lie.  P = 0
+ * zeroes dG.
+ *
+ * ttr_ttm_lookup_grad_input: ttr_ttm_lookup_step's structure with the slice staged transposed: the rows of a group are the
+ * (sample, dd) pairs of its samples in tiles of 64, K = (o, s) is the contiguous axis of dY and of G and N = R.  `G` is read with
+ * the four element strides g_strides under ttr_ttm_lookup_step's rules.  K is never split: every element of dX is one chain in
+ * increasing (o, s) fixed by O S and the dtype, so a row's bits do not depend on P, on the other samples or on the order inside
+ * a group.  Workspace: ttr_ttm_lookup_grad_input_workspace_bytes(P, I) (< 0 for P < 0 or an I outside 1 .. 2^31 - 1).  P = 0
+ * returns TTR_OK at once.
+ *
+ * Before any launch, with the output untouched: TTR_E_INVALID for a bad dtype, an extent < 1 (P < 0), a stride_idx < 1, a null
+ * pointer (xrow excepted) or an output that is one of the inputs; TTR_E_UNSUPPORTED for the strides of G, for D R, O S, P D, I or
+ * rows_x above 2^31 - 1 and for an operand of 2^57 elements or more (the queries return the same codes, < 0); TTR_E_WORKSPACE
+ * for a missing or short workspace.  Profiling kind: TTR_PROF_GEMM.
+ *
+ * ttr_segment_sum   out[b, :] = sum_{q = seg[b]}^{seg[b + 1] - 1} (w ? w[src(q)] : 1) * Y[src(q), :],   src(q) = perm ? perm[q] : q
+ *
+ * `Y` [P, C] and `out` [B, C] are contiguous, `w` [P] (or NULL: ones) has the dtype, `perm` [P] (or NULL) and `seg` [B + 1] are
+ * contiguous int64 device vectors, seg non-decreasing in 0 .. P.  A workgroup owns one segment and one block of columns (16-byte
+ * loads where C is a multiple of 16 bytes of elements and Y and out are 16-byte aligned); its four waves take consecutive quarters
+ * of the segment and are combined in wave order.  Accumulation is in fp64 with one rounding at the store (fp32: exact products;
+ * fp64: compensated sums), in a fixed order: the same call gives the same bits.  An empty segment gives zeros.  A segment is never
+ * split across workgroups: a very long one sits on ceil(C / block) of them.  seg is clamped to 0 .. P and a src outside 0 .. P - 1
+ * is skipped, never read.  Before any launch: TTR_E_INVALID for a bad dtype, B < 0, P < 0, C < 1, a null pointer (w and perm
+ * excepted; Y where P = 0) or an out that is one of the inputs; TTR_E_UNSUPPORTED for an operand of 2^57 elements or more.  B = 0
+ * returns TTR_OK at once.  Profiling kind: TTR_PROF_MISC.
+ */
+int64_t ttr_ttm_lookup_grad_core_slab_rows(int dtype, int64_t P, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S);
+int64_t ttr_ttm_lookup_grad_core_workspace_bytes(int dtype, int64_t P, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S);
+int ttr_ttm_lookup_grad_core(int dtype, int64_t P, int64_t rows_x, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S,
+                             const void* X, const void* xrow, const void* dY, const void* idx, int64_t stride_idx,
+                             const void* perm, void* dG, void* oob_flag, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t ttr_ttm_lookup_grad_input_workspace_bytes(int64_t P, int64_t I);
+int ttr_ttm_lookup_grad_input(int dtype, int64_t P, int64_t D, int64_t R, int64_t I, int64_t O, int64_t S, const void* dY,
+                              const void* G, const int64_t* g_strides, const void* idx, int64_t stride_idx, const void* perm,
+                              void* dX, void* oob_flag, void* workspace, int64_t workspace_bytes, void* stream);
+int ttr_segment_sum(int dtype, int64_t B, int64_t P, int64_t C, const void* Y, const void* w, const void* perm, const void* seg,
+                    void* out, void* stream);
 
 /*
  * One core of a TT-matrix product that stays in TT format (added under ABI 17; ttalgebra.py `tt_apply`, `tt_matmul`; DESIGN

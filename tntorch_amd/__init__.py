@@ -17,7 +17,7 @@ convolution of two trains (``tn.convolve``), and the Boolean layer: ``tn.automat
 ``tn.undo_anova_decomposition``, ``tn.truncate_anova``, ``tn.sobol``, ``tn.mean_dimension`` and ``tn.dimension_distribution``,
 and drawing index vectors from a train read as an unnormalised mass function: ``tn.sample``, and the matrix formats of
 ``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``, and a batch of rows of a TT-matrix
-(``tn.tt_lookup``: the embedding table), and the products that stay in TT format (``tn.tt_apply``: a TT-matrix applied to a
+(``tn.tt_lookup``: the embedding table; ``tn.tt_embedding`` / ``tn.tt_embedding_bag``: the same table, trainable on the device), and the products that stay in TT format (``tn.tt_apply``: a TT-matrix applied to a
 train, ``tn.tt_matmul``, ``tn.tt_transpose``), and the solver that inverts them: ``tn.tt_solve``, fixed-rank ALS for ``A x = b``
 with a symmetric positive definite ``TTMatrix`` and a train ``b`` (the three-layer environment fused into one kernel), and the extreme
 eigenpair of a symmetric ``TTMatrix``: ``tn.tt_eigsh``, fixed-rank ALS whose local LOBPCG steps are two fused kernels, and gradient-based fitting (``autodiff.py``):
@@ -33,6 +33,7 @@ from .create import *  # noqa: F401,F403
 from .metrics import *  # noqa: F401,F403
 from .matrix import *  # noqa: F401,F403
 from .lookup import *  # noqa: F401,F403
+from .embedding import *  # noqa: F401,F403
 from .ttalgebra import *  # noqa: F401,F403
 from .ttsolve import *  # noqa: F401,F403
 from .tteigs import *  # noqa: F401,F403
@@ -45,7 +46,7 @@ from .automata import *  # noqa: F401,F403
 from .logic import *  # noqa: F401,F403
 from .anova import *  # noqa: F401,F403
 from .autodiff import *  # noqa: F401,F403
-from . import autodiff, automata, logic, lookup, tteigs, ttsolve  # noqa: F401
+from . import autodiff, automata, embedding, logic, lookup, tteigs, ttsolve  # noqa: F401
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

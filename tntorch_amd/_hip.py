@@ -1776,6 +1776,110 @@ def ttm_lookup_step(X: torch.Tensor, xrow: Optional[torch.Tensor], G: torch.Tens
     return out
 
 
+def ttm_lookup_grad_core_slab_rows(dt: torch.dtype, P: int, D: int, R: int, I: int, O: int, S: int) -> int:
+    """K rows (sample, dd) one workgroup of ttr_ttm_lookup_grad_core sums (a function of these seven arguments only)."""
+    rows = int(lib().ttr_ttm_lookup_grad_core_slab_rows(dtype_code(dt), int(P), int(D), int(R), int(I), int(O), int(S)))
+    if rows < 0:
+        _check(rows, "ttr_ttm_lookup_grad_core_slab_rows")
+    return rows
+
+
+def ttm_lookup_grad_core_workspace_bytes(dt: torch.dtype, P: int, D: int, R: int, I: int, O: int, S: int) -> int:
+    """Bytes of workspace ttr_ttm_lookup_grad_core needs: the counts and ceil(P D / slab_rows) + I partial tiles."""
+    wsb = int(lib().ttr_ttm_lookup_grad_core_workspace_bytes(dtype_code(dt), int(P), int(D), int(R), int(I), int(O), int(S)))
+    if wsb < 0:
+        _check(wsb, "ttr_ttm_lookup_grad_core_workspace_bytes")
+    return wsb
+
+
+def ttm_lookup_grad_input_workspace_bytes(P: int, I: int) -> int:
+    """Bytes of workspace ttr_ttm_lookup_grad_input needs for a mode of size I (the counts of the groups)."""
+    wsb = int(lib().ttr_ttm_lookup_grad_input_workspace_bytes(int(P), int(I)))
+    if wsb < 0:
+        _check(wsb, "ttr_ttm_lookup_grad_input_workspace_bytes")
+    return wsb
+
+
+def _lookup_grad_indices(who: str, idx: torch.Tensor, perm: torch.Tensor, xrow: Optional[torch.Tensor], flag: torch.Tensor, device):
+    """(P, stride) of the index operands of the two gradient entries, checked as ttm_lookup_step checks them."""
+    assert idx.dim() == 1 and idx.dtype == torch.int64 and idx.device == device, who
+    P = idx.shape[0]
+    stride = int(idx.stride(0)) if P > 1 else 1
+    assert perm.dtype == torch.int64 and tuple(perm.shape) == (P,) and perm.device == device and perm.is_contiguous(), who
+    if xrow is not None:
+        assert xrow.dtype == torch.int64 and tuple(xrow.shape) == (P,) and xrow.device == device
+        assert P <= 1 or int(xrow.stride(0)) == stride, who + ": idx and xrow must have the same stride"
+    assert flag.dtype == torch.int32 and flag.numel() == 1 and flag.device == device
+    return P, stride
+
+
+@_on_device
+def ttm_lookup_grad_core(X: torch.Tensor, xrow: Optional[torch.Tensor], dY: torch.Tensor, idx: torch.Tensor, perm: torch.Tensor,
+                         flag: torch.Tensor, out: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ttm_lookup_grad_core: dG[r, i, o, s] = sum_{p: idx[p] = i} sum_dd X[xrow[p], dd, r] dY[p, dd, o, s] for a contiguous X
+    [rows_x, D, R] and dY (P D O S contiguous elements, read as [P, D, O, S]) into ``out``, a contiguous [R, I, O, S] tensor (it
+    gives I, O and S).  ``idx`` / ``xrow`` (or None: X[p]) as in ttm_lookup_step; ``perm``: the contiguous int64 sample ids grouped
+    by wrapped idx (``torch.sort(idx mod I, stable=True).indices``).  Nothing is read back: a bad index ORs ``flag`` and leaves
+    ``out`` unwritten.  ``workspace``: uint8, at least ``ttm_lookup_grad_core_workspace_bytes``."""
+    dt = dtype_code(X.dtype)
+    assert X.dim() == 3 and X.is_contiguous() and dY.dtype == X.dtype and dY.device == X.device and dY.is_contiguous()
+    rows_x, D, R = X.shape
+    assert out.dim() == 4 and out.shape[0] == R and out.is_contiguous() and out.dtype == X.dtype and out.device == X.device
+    I, O, S = out.shape[1], out.shape[2], out.shape[3]
+    P, stride = _lookup_grad_indices("ttm_lookup_grad_core", idx, perm, xrow, flag, X.device)
+    assert dY.numel() == P * D * O * S
+    ws = workspace if workspace is not None else _workspace(ttm_lookup_grad_core_workspace_bytes(X.dtype, P, D, R, I, O, S), X.device)
+    _call("ttr_ttm_lookup_grad_core", dt, P, rows_x, D, R, I, O, S, X.data_ptr(), _ptr(xrow), dY.data_ptr(), idx.data_ptr(), stride,
+          perm.data_ptr(), out.data_ptr(), flag.data_ptr(), ws.data_ptr(), int(ws.numel()))
+    return out
+
+
+@_on_device
+def ttm_lookup_grad_input(dY: torch.Tensor, G: torch.Tensor, idx: torch.Tensor, perm: torch.Tensor, flag: torch.Tensor,
+                          out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_ttm_lookup_grad_input: dX[p, dd, r] = sum_{o, s} dY[p, dd, o, s] G[r, idx[p], o, s] for dY (P D O S contiguous elements,
+    read as [P, D, O, S]) and G [R, I, O, S] (passed with the strides it has, as to ttm_lookup_step) -> dX [P, D, R].  ``idx`` and
+    ``perm`` as in ttm_lookup_grad_core.  ``out``: a contiguous tensor of P D R elements; ``workspace``: uint8, at least
+    ``ttm_lookup_grad_input_workspace_bytes(P, I)``."""
+    dt = dtype_code(G.dtype)
+    assert G.dim() == 4 and dY.dtype == G.dtype and dY.device == G.device and dY.is_contiguous()
+    R, I, O, S = G.shape
+    P, stride = _lookup_grad_indices("ttm_lookup_grad_input", idx, perm, None, flag, G.device)
+    assert dY.numel() % max(P * O * S, 1) == 0
+    D = dY.numel() // (P * O * S) if P else 1
+    if out is None:
+        out = torch.empty((P, D, R), dtype=G.dtype, device=G.device)
+    assert out.numel() == P * D * R and out.is_contiguous() and out.dtype == G.dtype and out.device == G.device
+    if P == 0:
+        return out
+    ws = workspace if workspace is not None else _workspace(ttm_lookup_grad_input_workspace_bytes(P, I), G.device)
+    _call("ttr_ttm_lookup_grad_input", dt, P, D, R, I, O, S, dY.data_ptr(), G.data_ptr(), _i64(G.stride()), idx.data_ptr(), stride,
+          perm.data_ptr(), out.data_ptr(), flag.data_ptr(), ws.data_ptr(), int(ws.numel()))
+    return out
+
+
+@_on_device
+def segment_sum(Y: torch.Tensor, seg: torch.Tensor, w: Optional[torch.Tensor] = None, perm: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ttr_segment_sum: out[b, :] = sum_{q = seg[b]}^{seg[b + 1] - 1} (w[src(q)] or 1) Y[src(q), :], src(q) = perm[q] (or q), for
+    a contiguous Y [P, C], contiguous int64 device vectors ``seg`` [B + 1] (non-decreasing in 0 .. P) and ``perm`` [P], and ``w``
+    [P] of Y's dtype -> out [B, C].  fp64 accumulation, one rounding, a fixed order."""
+    dt = dtype_code(Y.dtype)
+    assert Y.dim() == 2 and Y.is_contiguous() and Y.shape[1] >= 1
+    P, C = Y.shape
+    assert seg.dim() == 1 and seg.numel() >= 1 and seg.dtype == torch.int64 and seg.device == Y.device and seg.is_contiguous()
+    B = seg.numel() - 1
+    for t, ty in ((w, Y.dtype), (perm, torch.int64)):
+        assert t is None or (tuple(t.shape) == (P,) and t.dtype == ty and t.device == Y.device and t.is_contiguous())
+    if out is None:
+        out = torch.empty((B, C), dtype=Y.dtype, device=Y.device)
+    assert out.numel() == B * C and out.is_contiguous() and out.dtype == Y.dtype and out.device == Y.device
+    if B == 0:
+        return out
+    _call("ttr_segment_sum", dt, B, P, C, _ptr(Y) if P else None, _ptr(w), _ptr(perm), seg.data_ptr(), out.data_ptr())
+    return out
+
+
 @_on_device
 def env_half_apply(Phi: torch.Tensor, X: torch.Tensor, G: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ttr_env_half_apply: Phi [R, A, R'] (contiguous), X [R', J, S'] and G [A, I, J, A'] (both passed with the strides they have:

@@ -2310,9 +2310,20 @@ def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torc
     input of the next as it lies.  Only a step's input and output are alive at a time.  A row outside [-rows, rows) has a first
     digit outside its mode: the launches' shared flag word (d = 1: a torch comparison) is read once at the end -- the only
     host synchronisation -- and IndexError is raised instead of a result."""
-    P = rows1d.shape[0]
+    out, flag, _ = tt_lookup_steps(cores, _hostops.lookup_digits(cores, rows1d))
+    if bool(flag.item()):  # the one host read of the call
+        raise IndexError("tt_lookup: a row index lies outside the matrix")
+    return out
+
+
+def tt_lookup_steps(cores: Sequence[torch.Tensor], digits: torch.Tensor, keep: Optional[Sequence[bool]] = None):
+    """The launches of ``tt_lookup_chain`` for the digit table ``digits`` [P, d], nothing read back: ``(out [P, prod O_k], flag,
+    kept)`` with ``flag`` the device word (int32 [1]; d = 1: a bool scalar) that is non-zero when a first digit lies outside its
+    mode (``out`` is then not to be used) and ``kept[k]`` the input Z_k [P, D_k, r_k] of the step on core k (0-based, k >= 2) where
+    ``keep[k]``, else None -- what the backward of ``autodiff.tt_rows`` needs for that core's gradient."""
+    P = digits.shape[0]
     dev = cores[0].device
-    digits = _hostops.lookup_digits(cores, rows1d)
+    kept: List[Optional[torch.Tensor]] = [None] * len(cores)
     G1 = cores[0][0]                                               # [I_1, O_1, r_1]
     if len(cores) == 1:
         i1 = digits[:, 0]
@@ -2324,12 +2335,18 @@ def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torc
         X, xrow = G1.contiguous(), digits[:, 0]
         for k in range(1, len(cores)):
             G = cores[k].contiguous()
-            X = _hip.ttm_lookup_step(X.view(X.shape[0], -1, G.shape[0]), xrow, G, digits[:, k], flag, workspace=ws)
+            X = X.view(X.shape[0], -1, G.shape[0])
+            if keep is not None and keep[k] and k >= 2:
+                kept[k] = X
+            X = _hip.ttm_lookup_step(X, xrow, G, digits[:, k], flag, workspace=ws)
             xrow = None
         out = X.view(P, -1)
-    if bool(flag.item()):  # the one host read of the call
-        raise IndexError("tt_lookup: a row index lies outside the matrix")
-    return out
+    return out, flag, kept
+
+
+ttm_lookup_grad_core = _hip.ttm_lookup_grad_core
+ttm_lookup_grad_input = _hip.ttm_lookup_grad_input
+segment_sum = _hip.segment_sum
 
 
 # ---------------------------------------------------------------------------------------------- tt_solve (ttsolve.py)

@@ -1024,6 +1024,36 @@ def tt_lookup_chain(cores: Sequence[torch.Tensor], rows1d: torch.Tensor) -> torc
     return Z.reshape(P, -1)
 
 
+def ttm_lookup_grad_core(X: torch.Tensor, xrow: Optional[torch.Tensor], dY: torch.Tensor, idx: torch.Tensor, I: int) -> torch.Tensor:
+    """Mirror of ttr_ttm_lookup_grad_core: X [rows_x, D, R], dY [P, D, O, S], idx [P] (wrapped) -> dG [R, I, O, S],
+    dG[r, i, o, s] = sum_{p: idx[p] = i} sum_dd X[xrow[p], dd, r] dY[p, dd, o, s]; a slice without samples is zero."""
+    Xg = X if xrow is None else X[xrow]
+    v = torch.remainder(idx.to(torch.int64), I)
+    dG = torch.zeros((X.shape[2], I, dY.shape[2], dY.shape[3]), dtype=X.dtype, device=X.device)
+    return dG.index_add_(1, v, torch.einsum("pdr,pdos->rpos", Xg, dY))
+
+
+def ttm_lookup_grad_input(dY: torch.Tensor, G: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """Mirror of ttr_ttm_lookup_grad_input: dY [P, D, O, S], G [R, I, O, S], idx [P] (wrapped) -> dX [P, D, R],
+    dX[p, dd, r] = sum_{o, s} dY[p, dd, o, s] G[r, idx[p], o, s]."""
+    v = torch.remainder(idx.to(torch.int64), G.shape[1])
+    return torch.einsum("pdos,rpos->pdr", dY, G[:, v])
+
+
+def segment_sum(Y: torch.Tensor, seg: torch.Tensor, w: Optional[torch.Tensor] = None, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mirror of ttr_segment_sum: Y [P, C], seg [B + 1] (non-decreasing in 0 .. P) -> out [B, C], out[b] = the sum over
+    q = seg[b] .. seg[b + 1] - 1 of (w[src(q)] or 1) Y[src(q)], src(q) = perm[q] (or q).  An ``index_add_``: differentiable in Y
+    and w; an empty segment gives zeros."""
+    P, B = Y.shape[0], seg.shape[0] - 1
+    q = torch.arange(P, device=Y.device)
+    bag = torch.searchsorted(seg[1:].contiguous(), q, right=True)      # the segment of position q; B at and past seg[B]
+    live = (q >= seg[0]) & (bag < B)
+    src = q if perm is None else perm
+    rows = Y[src] if w is None else Y[src] * w[src][:, None]
+    out = torch.zeros((B, Y.shape[1]), dtype=Y.dtype, device=Y.device)
+    return out.index_add_(0, bag[live], rows[live])
+
+
 # ---------------------------------------------------------------------------------------------- tt_solve (ttsolve.py; DESIGN section 29)
 def gemm2d(A: torch.Tensor, B: torch.Tensor, transA: bool = False, transB: bool = False) -> torch.Tensor:
     return (A.t() if transA else A) @ (B.t() if transB else B)

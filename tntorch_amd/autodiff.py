@@ -330,6 +330,103 @@ def tt_matvec(cores: Sequence[torch.Tensor], x2d: torch.Tensor, ops) -> torch.Te
     return _TTMatvec.apply(ops, x2d, *cores)
 
 
+# ---------------------------------------------------------------------------------------------- tt_embedding, tt_embedding_bag
+class _TTRows(torch.autograd.Function):
+    """out = pool(M[rows]) for the TT-matrix with the device cores G_k [r_k, I_k, O_k, r_{k+1}] (r_0 = r_d = 1): the chain of
+    ``_hipops.tt_lookup_steps`` on the digit table, then -- with ``seg`` -- one ``ttr_segment_sum`` over the bags.  ``seg``
+    (int64 [B + 1] or None: no pooling), ``weights`` ([P] or None), ``lengths`` ([B] in the dtype, the divisors of "mean", or
+    None) and ``bad`` (a device bool: the offsets are invalid; or None) carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, rows1d, seg, weights, lengths, bad, *cores):
+        from . import _hipops, _hostops
+
+        needs = [bool(n) for n in ctx.needs_input_grad[5:]]
+        digits = _hostops.lookup_digits(cores, rows1d)
+        # Z_k is needed by dG_k only; Z_1 = G_1[0, i_1] is read through the row map, never kept
+        Y, flag, kept = _hipops.tt_lookup_steps(cores, digits, keep=needs)
+        out = Y if seg is None else _hipops.segment_sum(Y, seg, w=weights)
+        if lengths is not None:
+            out = out / lengths[:, None]
+        words = torch.stack([flag.reshape(()).to(torch.int32), (bad if bad is not None else flag.new_zeros(())).to(torch.int32)])
+        oob, bad_offsets = words.tolist()  # the one host read of the call
+        if bad_offsets:
+            raise ValueError("tt_embedding_bag: the offsets must start at 0, not decrease and not pass the number of rows")
+        if oob:
+            raise IndexError("tt_lookup: a row index lies outside the matrix")
+        ctx.d = len(cores)
+        ctx.pooled = (seg is not None, weights is not None, lengths is not None)
+        ctx.save_for_backward(*cores, *[z for z in kept if z is not None], digits,
+                              *[t for t in (seg, weights, lengths) if t is not None])
+        ctx.kept_at = [k for k, z in enumerate(kept) if z is not None]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import _hipops
+
+        d, saved = ctx.d, list(ctx.saved_tensors)
+        cores = saved[:d]
+        kept = dict(zip(ctx.kept_at, saved[d:d + len(ctx.kept_at)]))
+        digits = saved[d + len(ctx.kept_at)]
+        rest = saved[d + len(ctx.kept_at) + 1:]
+        seg = rest.pop(0) if ctx.pooled[0] else None
+        weights = rest.pop(0) if ctx.pooled[1] else None
+        lengths = rest.pop(0) if ctx.pooled[2] else None
+        needs = [bool(n) for n in ctx.needs_input_grad[5:]]
+        grads: List[Optional[torch.Tensor]] = [None] * d
+        P, dev, dt = digits.shape[0], g.device, g.dtype
+        # dY [P, cols]: the gradient of each sample's row (torch ops on the device; nothing is read back in here)
+        if lengths is not None:
+            g = g / lengths[:, None]
+        if seg is not None:
+            bag = torch.searchsorted(seg[1:].contiguous(), torch.arange(P, device=dev), right=True)
+            g = g.index_select(0, bag)
+            if weights is not None:
+                g = g * weights[:, None]
+        dY = g.contiguous()
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)  # (the forward validated the digits: it stays 0 and is not read)
+        for k in range(d - 1, 0, -1):
+            if not any(needs[:k + 1]):  # nothing from here down needs a gradient: the chain ends
+                break
+            G = cores[k].contiguous()
+            R, I, O, S = G.shape
+            col = digits[:, k]
+            perm = torch.sort(col, stable=True).indices  # on the device; shared by the two launches of this step
+            if needs[k]:
+                X, xrow = (cores[0][0].contiguous(), digits[:, 0]) if k == 1 else (kept[k], None)
+                grads[k] = _hipops.ttm_lookup_grad_core(X, xrow, dY, col, perm, flag,
+                                                        torch.empty((R, I, O, S), dtype=dt, device=dev))
+            if not any(needs[:k]):
+                break
+            dY = _hipops.ttm_lookup_grad_input(dY, G, col, perm, flag)  # dZ_{k-1} [P, D, R]: the next step's dY as it lies
+        if needs[0]:  # dG_1[0, i] = the sum of dZ_1[p] over the samples with i_1 = i: the stable groups of the first digit
+            I1 = cores[0].shape[1]
+            srt = torch.sort(digits[:, 0], stable=True)
+            seg0 = torch.searchsorted(srt.values, torch.arange(I1 + 1, device=dev))
+            grads[0] = _hipops.segment_sum(dY.view(P, -1), seg0, perm=srt.indices).view(cores[0].shape)
+        return (None, None, None, None, None) + tuple(grads)
+
+
+def tt_rows(cores: Sequence[torch.Tensor], rows1d: torch.Tensor, seg: Optional[torch.Tensor] = None,
+            weights: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+            bad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable rows ``rows1d`` [P] of the TT-matrix with the device cores G_k [r_k, I_k, O_k, r_{k+1}] -> [P, cols], or
+    -- with ``seg`` (int64 [B + 1], the bounds of the bags) -- their sums over the bags, weighted by ``weights`` [P] and divided
+    by ``lengths`` [B] -> [B, cols].  ``bad``: a device bool, checked (ValueError) in the one host read of the call, next to the
+    out-of-range word (IndexError).
+
+    The forward is the launches of ``tt_lookup_chain`` (the same bits) and one ``ttr_segment_sum`` for the bags.  It keeps the
+    digit table and, for every core k >= 3 that requires grad, the state Z_{k-1} [P, O_1 .. O_{k-1}, r_{k-1}] that entered its
+    step: THAT is the memory cost of training (the plain lookup keeps one state at a time); Z_1 is read from the first core.  The
+    backward synchronises nothing: per step one stable ``torch.sort`` of the digit column on the device (no plan, no counts on
+    the host), ``ttr_ttm_lookup_grad_core`` where the core requires grad and ``ttr_ttm_lookup_grad_input`` where an earlier one
+    does, and one ``ttr_segment_sum`` over the groups of the first digit for the first core.  A frozen core costs no launch and
+    gets no gradient.  No double backward, no gradient of ``weights``."""
+    return _TTRows.apply(rows1d, seg, weights, lengths, bad, *cores)
+
+
 # ---------------------------------------------------------------------------------------------- autodiff.py:10-121
 def _parameters(tensors) -> list:
     from .tensor import Tensor

@@ -10,8 +10,9 @@ runs as a chain with the state ``Z_k [P, D_k, r_k]``, ``D_k = O_1 .. O_k``: ``Z_
 G_k[r, i_k(p), o, s]``.  The row-major output of a step is the next step's input as it lies.  On the device a step is one
 launch of ``ttr_ttm_lookup_step``: the samples are grouped by ``i_k`` so that those of a group share their slice of the core,
 and each group is a GEMM on the matrix cores.  On the CPU the chain is plain torch, and therefore differentiable in the cores.
-Not here: the backward on the device (a later change; it raises instead of cutting the graph), a CP-matrix lookup, the
-deduplication of repeated rows and a kernel for the whole chain.
+``tt_lookup`` itself refuses device cores that require grad (it raises instead of cutting the graph): the trainable lookup is
+``embedding.py``'s ``tt_embedding`` / ``tt_embedding_bag``.  Not here: a CP-matrix lookup, the deduplication of
+repeated rows and a kernel for the whole chain.
 """
 
 from __future__ import annotations
@@ -24,13 +25,10 @@ from .matrix import TTMatrix
 __all__ = ["tt_lookup"]
 
 
-def tt_lookup(tt_matrix: TTMatrix, rows) -> torch.Tensor:
-    """``tt_matrix.torch()[rows]`` -> ``rows.shape + (cols,)`` on the cores' device in their dtype, without forming the matrix.
-    ``rows``: an integer tensor of any shape (int32 / int64, on the cores' device), or a list / tuple / numpy array of ints
-    (placed there); negative entries wrap as in torch, a row outside ``[-rows, rows)`` raises ``IndexError``.  On the device:
-    ``d - 1`` launches of ``ttr_ttm_lookup_step`` (``d = 1``: an ``index_select``) and one readback of the out-of-range word.
-    Neither operand is modified.  Under grad mode a device core that requires grad raises ``NotImplementedError``."""
-    who = "tt_lookup"
+def lookup_operands(who: str, tt_matrix, rows):
+    """The checks ``tt_lookup`` and the calls of ``embedding.py`` share: ``(cores, rows, cols)`` with ``rows`` an int32 / int64
+    tensor on the cores' device (a list / tuple / numpy array of ints is placed there) and ``cols`` the number of columns;
+    ``ValueError`` (``who`` names the caller) for anything else."""
     if not isinstance(tt_matrix, TTMatrix):
         raise ValueError("{}: the first argument must be a TTMatrix, got {}".format(who, type(tt_matrix).__name__))
     cores = tt_matrix.cores
@@ -58,6 +56,18 @@ def tt_lookup(tt_matrix: TTMatrix, rows) -> torch.Tensor:
     cols = 1
     for c in cores:
         cols *= int(c.shape[2])
+    return cores, rows, cols
+
+
+def tt_lookup(tt_matrix: TTMatrix, rows) -> torch.Tensor:
+    """``tt_matrix.torch()[rows]`` -> ``rows.shape + (cols,)`` on the cores' device in their dtype, without forming the matrix.
+    ``rows``: an integer tensor of any shape (int32 / int64, on the cores' device), or a list / tuple / numpy array of ints
+    (placed there); negative entries wrap as in torch, a row outside ``[-rows, rows)`` raises ``IndexError``.  On the device:
+    ``d - 1`` launches of ``ttr_ttm_lookup_step`` (``d = 1``: an ``index_select``) and one readback of the out-of-range word.
+    Neither operand is modified.  Under grad mode a device core that requires grad raises ``NotImplementedError``:
+    ``tn.tt_embedding`` is the same lookup, differentiable in the cores on every device."""
+    cores, rows, cols = lookup_operands("tt_lookup", tt_matrix, rows)
+    dtype, device = cores[0].dtype, cores[0].device
     shape = tuple(rows.shape) + (cols,)
     if rows.numel() == 0:
         return torch.zeros(shape, dtype=dtype, device=device)
