@@ -525,7 +525,12 @@ def eigh_topk(G: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor, torc
     multisection + twisted factorisation on the tridiagonal matrix, TSQR of the k vectors, back-transformation (ttr_tridiag,
     ttr_tri_eigsel, ttr_qr, ttr_tridiag_back).  Returns (X [batch, n, k] orthonormal, lam [batch, k] descending,
     rmin [batch] = the smallest |R_jj| of the orthonormalisation: well below 1 when two of the k vectors nearly coincided --
-    clustered or multiple eigenvalues, which this solver does not resolve; the caller decides)."""
+    clustered or multiple eigenvalues, which this solver does not resolve; the caller decides).
+    The size range: include/ttround_hip.h words the family as "symmetric matrices with 64 < n <= ttr_eigsel_max_n()" -- that is
+    where it is used and tuned (below it the single-workgroup eigensolvers are faster).  The contract of the three entry points
+    is wider: each accepts 2 <= n <= ttr_eigsel_max_n() (k <= min(64, n) for ttr_tri_eigsel) and refuses everything else with
+    TTR_E_UNSUPPORTED; this wrapper adds no check of its own (tests/test_eigsel_kernels_gpu.py drives the entry points
+    from n = 2)."""
     L = lib()
     dt = dtype_code(G.dtype)
     batch, n, _ = G.shape

@@ -37,7 +37,7 @@ struct TridiagArgs {
   T* tau;  // [batch][n]
 };
 
-// sum over the 512 threads, result in every thread (red: kTdWaves elements; the leading barrier protects its reuse)
+// sum over the kTdThreads (1024) threads, result in every thread (red: kTdWaves elements; the leading barrier protects its reuse)
 template <typename T>
 __device__ __forceinline__ T td_block_sum(T v, T* red) {
   v = wave_sum_dpp(v);
