@@ -58,7 +58,8 @@ extern "C" {
    ttr_gather_grad_stage_rows, and ttr_ttm_grad_input, ttr_ttm_grad_core_slab_rows, ttr_ttm_grad_core_workspace_bytes and
    ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose, and ttr_env_half_apply, and ttr_ritz_parts, ttr_ritz_workspace_bytes, ttr_ritz_gram and
    ttr_ritz_update, and ttr_ttm_lookup_grad_core_slab_rows, ttr_ttm_lookup_grad_core_workspace_bytes, ttr_ttm_lookup_grad_core,
-   ttr_ttm_lookup_grad_input_workspace_bytes, ttr_ttm_lookup_grad_input and ttr_segment_sum.  ttr_version() returns the value the library was built with; the Python
+   ttr_ttm_lookup_grad_input_workspace_bytes, ttr_ttm_lookup_grad_input and ttr_segment_sum, and ttr_eigh_trunc_pass and
+   ttr_project_flat (+ TTR_KNOB_FLAT_PASS; ttr_eigh_trunc and ttr_project keep their signatures and behaviour).  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -267,6 +268,18 @@ int ttr_eigh_trunc(int dtype, int64_t n, int64_t batch,
  * `delta2_dev` (optional, device pointer to ONE double): the bound delta^2 of the rank rule taken from device memory instead
  * of `delta2` -- tensor.py:2039-2051 computes delta from the norm of the last core and reads it back (`.item()`); an
  * eps-mode sweep that keeps it on the device enqueues every bond without a host synchronisation. */
+/* Pass 2 of the two-pass truncation for a caller that hands `skip_items` to ttr_project_flat as well: ttr_eigh_trunc, except that
+ * V of a pass-through item is NOT written (nobody reads the identity; 4 n^2 bytes per item).  Its sigma (= sigma_in: ttr_orth_fixup
+ * reads it), info and sweeps are written as usual.  TTR_KNOB_FLAT_PASS = 0: ttr_eigh_trunc itself. */
+int ttr_eigh_trunc_pass(int dtype, int64_t n, int64_t batch,
+                        const void* G, int64_t ldg, int64_t strideG, int64_t gparts, int64_t stride_gpart,
+                        void* V, int64_t ldv, int64_t strideV,
+                        void* sigma, int64_t stride_sigma,
+                        int32_t* info,
+                        int eig_mode, int use_delta, double delta2, const double* delta2_dev, int64_t rmax,
+                        int abs_floor, int32_t* sweeps,
+                        const int32_t* skip_items, const void* sigma_in, int64_t stride_sigma_in,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * Pass 1 of a batch-mode bond with 40 <= n <= 64 rows and a rank cap r <= 32, r < n (ttr_eigh_top_ok): round.py:96, 147-158 with
@@ -447,7 +460,8 @@ int ttr_rotgram(int dtype, int64_t R, int64_t n, int64_t batch, const void* M, i
  *     tail(r) <= delta^2 - E and tail(r - 1) > delta^2 + E (rank cap binding, r = keep: only the latter) -- pass 2 would select
  *     the same rank.  (fp32 with eps = 1e-4: E exceeds delta^2, nothing qualifies; fp64 trains do.)
  * ttr_rotgram skips items with skip[b] != 0 (their G is not written) and ttr_eigh_trunc passes them through
- * (`skip_items`: V = I, sigma = sigma_in, rank rule as usual on sigma_in).
+ * (`skip_items`: V = I, sigma = sigma_in, rank rule as usual on sigma_in).  The sweep calls ttr_eigh_trunc_pass and
+ * ttr_project_flat instead, which leave the identity out (TTR_KNOB_FLAT_PASS).
  */
 int ttr_spectrum_flat(int dtype, int64_t n, int64_t batch, const void* sigma, int64_t stride_sigma, int64_t keep, double thr,
                       int use_delta, double delta2, const double* delta2_dev, int32_t* flat, const int32_t* rows32, void* stream);
@@ -461,6 +475,19 @@ int ttr_project(int dtype, int64_t R, int64_t n, int64_t ro, int64_t batch,
                 const void* sigma, int64_t stride_sigma, int scale_right,
                 void* right, int64_t ldr, int64_t strideR,
                 void* left, int64_t ldl, int64_t strideL, const int32_t* rows32, void* stream);
+/* ttr_project with the pass-through flags of the two-pass truncation.  `flat` (optional device int32 [batch]: the `skip` of
+ * ttr_rotgram, the `skip_items` of ttr_eigh_trunc_pass) and `sigma1` (pass 1's sigma, `stride_sigma1` elements per item): an item
+ * with flat[b] != 0 has V2 = I and sigma = sigma1 by construction, so neither V2 nor sigma is loaded and no V1 V2 is formed for it --
+ * U = V1[:, :ro], scales from sigma1: the bits of the product with the identity.  Items with flat[b] == 0, and every item when
+ * `flat` or `V1` is NULL or TTR_KNOB_FLAT_PASS is 0, are ttr_project's. */
+int ttr_project_flat(int dtype, int64_t R, int64_t n, int64_t ro, int64_t batch,
+                     const void* M, int64_t ldm, int64_t strideM,
+                     const void* V1, int64_t ldv1, int64_t strideV1,
+                     const void* V2, int64_t ldv2, int64_t strideV2,
+                     const void* sigma, int64_t stride_sigma, int scale_right,
+                     void* right, int64_t ldr, int64_t strideR,
+                     void* left, int64_t ldl, int64_t strideL, const int32_t* rows32,
+                     const int32_t* flat, const void* sigma1, int64_t stride_sigma1, void* stream);
 
 /*
  * The same fused kernels for TALL matrices (rows x n, n <= 64, row-major): the unfoldings a dense right-to-left TT-SVD
@@ -691,6 +718,12 @@ int ttr_debug_set_qr_stamps(void* device_buffer);
  *                      single-step kernel: rank-revealing pair steps, so the last bits of R differ (tests, and the A/B of the
  *                      first core of a sweep); the workspace layout is the 4-wave one either way. */
 #define TTR_KNOB_QR_PAIR4 20
+/*   TTR_KNOB_FLAT_PASS  1 (default) = the pass-through items of the two-pass truncation (flat kept spectrum, ttr_spectrum_flat)
+ *                      skip the identity round trip: ttr_eigh_trunc_pass does not write their V, and ttr_project_flat takes
+ *                      U = V1[:, :ro] and 1 / sigma from pass 1's sigma for them without loading V2 or sigma or forming V1 V2.  The
+ *                      product with an exact identity adds exact zeros to one exact term: same results bit for bit.  0 =
+ *                      ttr_eigh_trunc_pass writes V = I as ttr_eigh_trunc does and ttr_project_flat ignores its flags (A/B). */
+#define TTR_KNOB_FLAT_PASS 21
 int ttr_debug_set_knob(int knob, int value);
 int ttr_prof_enable(int on);   /* 0 = off, 1 = per-kind device times, 2 = times + executed-work census (ttr_prof_collect_work) */
 /* Synchronises the recorded events; fills total milliseconds and launch counts per kind; resets. */

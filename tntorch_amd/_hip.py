@@ -460,11 +460,13 @@ def qr_apply(f: QrFactors, C: Optional[torch.Tensor] = None, kcols: Optional[int
 def eigh_trunc(
     G: torch.Tensor, eig_mode: int, use_delta: bool, delta2: float, rmax: int, abs_floor: int = 1,
     sweeps: Optional[torch.Tensor] = None, delta2_dev: Optional[torch.Tensor] = None,
-    skip_items: Optional[torch.Tensor] = None, sigma_in: Optional[torch.Tensor] = None,
+    skip_items: Optional[torch.Tensor] = None, sigma_in: Optional[torch.Tensor] = None, skip_lean: bool = False,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Eigen-decomposition of symmetric [batch, n, n] + rank rule.  Returns V (columns sorted by
     decreasing sigma), sigma [batch, n], info [batch] int32 (rank, or 0 for the zero guard).
-    ``G`` may also be [batch, parts, n, n] (contiguous): split-K partials of a Gram kernel, summed on load."""
+    ``G`` may also be [batch, parts, n, n] (contiguous): split-K partials of a Gram kernel, summed on load.
+    ``skip_lean``: ttr_eigh_trunc_pass -- V of the ``skip_items`` is left unwritten (the caller hands the same flags to
+    ``project(flat=...)``, which does not read it)."""
     L = lib()
     dt = dtype_code(G.dtype)
     gparts, sGp = 1, 0
@@ -483,7 +485,7 @@ def eigh_trunc(
     wsb = L.ttr_eigh_workspace_bytes(dt, n, batch)
     ws = _workspace(wsb, G.device)
     rmax = int(min(max(int(rmax), 1), 2**31 - 1))
-    _call("ttr_eigh_trunc", dt, n, batch, G.data_ptr(), ldg, sG, gparts, sGp, V.data_ptr(), n, n * n, sigma.data_ptr(), n,
+    _call("ttr_eigh_trunc_pass" if skip_lean else "ttr_eigh_trunc", dt, n, batch, G.data_ptr(), ldg, sG, gparts, sGp, V.data_ptr(), n, n * n, sigma.data_ptr(), n,
           info.data_ptr(), eig_mode, int(bool(use_delta)), float(delta2), _ptr(delta2_dev), rmax, int(abs_floor),
           _ptr(sweeps), _ptr(skip_items), _ptr(sigma_in), sigma_in.shape[-1] if sigma_in is not None else 0, _ptr(ws), wsb)
     return V, sigma, info
@@ -704,9 +706,12 @@ def rowgram(M: torch.Tensor, V1: Optional[torch.Tensor] = None, skip: Optional[t
 @_on_device
 def project(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, sigma: Optional[torch.Tensor], ro: int,
             scale_right: bool, out: Optional[torch.Tensor] = None, want_left: bool = True,
-            rows32: Optional[torch.Tensor] = None):
+            rows32: Optional[torch.Tensor] = None, flat: Optional[torch.Tensor] = None,
+            sigma1: Optional[torch.Tensor] = None):
     """right [batch, ro, n] = diag(1/sigma) U^T M and left [batch, R, ro] = U diag(sigma) with U = V1 V2[:, :ro]
-    (ttr_project; ``scale_right=False``: right = U^T M, left = U).  ``out``: optional contiguous destination of right."""
+    (ttr_project_flat; ``scale_right=False``: right = U^T M, left = U).  ``out``: optional contiguous destination of right.
+    ``flat`` / ``sigma1``: the pass-through flags of the two-pass truncation and pass 1's sigma -- flagged items take
+    U = V1[:, :ro] and their scales from ``sigma1``; their V2 and sigma are not read."""
     dt = dtype_code(M.dtype)
     M, ldm, sM = _mat(M)
     batch, R, n = M.shape
@@ -727,8 +732,12 @@ def project(M: torch.Tensor, V1: Optional[torch.Tensor], V2: torch.Tensor, sigma
     if sigma is not None:
         sigma = sigma.contiguous()
         sp, ss = sigma.data_ptr(), sigma.shape[-1]
-    _call("ttr_project", dt, R, n, ro, batch, M.data_ptr(), ldm, sM, v1p, ldv1, sV1, V2.data_ptr(), ldv2, sV2, sp, ss,
-          int(bool(scale_right)), right.data_ptr(), n, ro * n, _ptr(left), ro, R * ro, _ptr(rows32))
+    s1p, s1s = None, 0
+    if flat is not None:
+        sigma1 = sigma1.contiguous()
+        s1p, s1s = sigma1.data_ptr(), sigma1.shape[-1]
+    _call("ttr_project_flat", dt, R, n, ro, batch, M.data_ptr(), ldm, sM, v1p, ldv1, sV1, V2.data_ptr(), ldv2, sV2, sp, ss,
+          int(bool(scale_right)), right.data_ptr(), n, ro * n, _ptr(left), ro, R * ro, _ptr(rows32), _ptr(flat), s1p, s1s)
     return right, left
 
 

@@ -680,17 +680,18 @@ def truncate(
     return _truncate_gemm(M, cut, gram, delta, right_alloc, scratch_ok)
 
 
-def _fused_eigs(G, rotgram, cut, st, top=None, delta2_dev=None, rows32=None):
-    """The solver step of both fused sweeps, from the first Gram matrix ``G`` to the rank rule: (V1, V, sigma, info).  'svd': pass-1
-    eigenvectors V1 -> per-item flat-spectrum flags -> ``rotgram(V1, flat)``, the Gram matrix of the ROTATED rows / columns ->
-    Jacobi.  'eig': one QL solve of G, V1 None.  Row sweep only: ``top``, its top-r solver's pass 1 (V1, sigma1, flags or None)."""
+def _fused_eigs(G, rotgram, cut, st, top=None, delta2_dev=None, rows32=None, skip_lean=False):
+    """The solver step of both fused sweeps, from the first Gram matrix ``G`` to the rank rule: (V1, V, sigma, info, sigma1, flat).
+    'svd': pass-1 eigenvectors V1 -> per-item flat-spectrum flags -> ``rotgram(V1, flat)``, the Gram matrix of the ROTATED rows /
+    columns -> Jacobi.  'eig': one QL solve of G, V1 None.  Row sweep only: ``top``, its top-r solver's pass 1 (V1, sigma1, flags or
+    None), and ``skip_lean``: V of the flat items is left unwritten (its projection takes ``flat`` and ``sigma1``)."""
     algorithm, left_ortho, batch, rmax, want_trace, k, use_delta, delta2, cap, rcap = cut
     if algorithm == "eig":
         st.lap("Time (gram):")
         V, sig, info = _hip.eigh_trunc(G, _hip.EIG_REF, use_delta, delta2, cap,
                                        abs_floor=_hip.SOLVER_TRIDIAG, delta2_dev=delta2_dev)
         st.lap("Time (symmetric EIG):")
-        return None, V, sig, info
+        return None, V, sig, info, None, None
     if top is not None:
         V1, sig1, flat = top
     else:
@@ -706,9 +707,9 @@ def _fused_eigs(G, rotgram, cut, st, top=None, delta2_dev=None, rows32=None):
         flat = _hip.spectrum_flat(sig1, rcap, FLAT_SPECTRUM_THR, use_delta, delta2, delta2_dev, rows32=rows32)
     V, sig, info = _hip.eigh_trunc(rotgram(V1, flat), _hip.EIG_RAW, use_delta, delta2, cap,
                                    abs_floor=_hip.SOLVER_JACOBI_LIVE, delta2_dev=delta2_dev,
-                                   skip_items=flat, sigma_in=sig1 if flat is not None else None)
+                                   skip_items=flat, sigma_in=sig1 if flat is not None else None, skip_lean=skip_lean)
     st.lap("Time (SVD):")   # (both Gram passes + both solvers)
-    return V1, V, sig, info
+    return V1, V, sig, info, sig1, flat
 
 
 def _truncate_rows64(M, cut, gram, right_alloc, delta2_dev, rows32) -> Truncation:
@@ -737,14 +738,16 @@ def _truncate_rows64(M, cut, gram, right_alloc, delta2_dev, rows32) -> Truncatio
             # batch mode: the launch's flags are the pass-through flags already (1: top-r path; 2: declined there, but the
             # full decomposition's kept sigma pass the same test) -- include/ttround_hip.h: ttr_eigh_top
             top = (V1, sig1, top_flat if batch else None)
-    V1, V, sig, info = _fused_eigs(G, lambda v1, flat: _hip.rowgram(M, v1, skip=flat, rows32=rows32), cut, st, top, delta2_dev, rows32)
+    V1, V, sig, info, sig1, flat = _fused_eigs(G, lambda v1, flat: _hip.rowgram(M, v1, skip=flat, rows32=rows32), cut, st, top,
+                                               delta2_dev, rows32, skip_lean=True)
     # ``delta2_dev``: the rank stays on the device -- factors at the cap, the columns beyond info[b] zeroed in place
     deferred = delta2_dev is not None
     r = rcap if deferred else _select_rank(info, batch, rmax, k)
     if r == 0:
         return _zero_truncation(M, gtr)
     dst = right_alloc(r) if right_alloc is not None else None
-    right, left = _hip.project(M, V1, V, sig, r, scale_right=not left_ortho, out=dst, rows32=rows32)
+    # (flat items: U = V1[:, :r] and pass 1's sigma -- their V was not written; ``sig`` still holds their sigma for orth_fixup)
+    right, left = _hip.project(M, V1, V, sig, r, scale_right=not left_ortho, out=dst, rows32=rows32, flat=flat, sigma1=sig1)
     if algorithm == "svd" and not left_ortho:
         # (see ``_truncate_gemm``; deferred: not the rows that are cut away)
         _hip.orth_fixup(right, sig, r, k * torch.finfo(M.dtype).eps, rank_dev=info if deferred else None)
@@ -763,7 +766,7 @@ def _truncate_cols64(M, cut, gram, consume) -> Truncation:
     st = _Stage()
     G0 = gram if gram is not None else _hip.colgram(M)
     gtr = _gram_trace(G0) if want_trace else None
-    V1, V, sig, info = _fused_eigs(G0, lambda v1, flat: _hip.colgram(M, v1, skip=flat), cut, st)
+    V1, V, sig, info, _, _ = _fused_eigs(G0, lambda v1, flat: _hip.colgram(M, v1, skip=flat), cut, st)
     r = _select_rank(info, batch, rmax, k)
     if r == 0:
         return _zero_truncation(M, gtr)

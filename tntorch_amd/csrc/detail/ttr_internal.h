@@ -55,7 +55,7 @@ int eigh_dispatch(int dtype, int64_t n, int64_t batch, const void* G, int64_t ld
                   int64_t stride_gpart, void* V, int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma, int32_t* info, int eig_mode,
                   int use_delta, double delta2, int64_t rmax, int abs_floor, int32_t* sweeps, void* ws,
                   int64_t ws_bytes, hipStream_t stream, const double* delta2_dev = nullptr, const int32_t* skip_items = nullptr,
-                  const void* sigma_in = nullptr, int64_t stride_sigma_in = 0);
+                  const void* sigma_in = nullptr, int64_t stride_sigma_in = 0, int skip_lean = 0);
 int eigh_top_dispatch(int dtype, int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts,
                       int64_t stride_gpart, void* V, int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma, int32_t* info,
                       int64_t r, double thr, int32_t* flat, hipStream_t stream, int need_all);
@@ -88,7 +88,8 @@ int sweep_project_dispatch(int dtype, int64_t R, int64_t n, int64_t ro, int64_t 
                            int64_t strideM, const void* V1, int64_t ldv1, int64_t strideV1, const void* V2, int64_t ldv2,
                            int64_t strideV2, const void* sigma, int64_t stride_sigma, int scale_right, void* right,
                            int64_t ldr, int64_t strideR, void* left, int64_t ldl, int64_t strideL, hipStream_t stream,
-                           const int32_t* rows32 = nullptr);
+                           const int32_t* rows32 = nullptr, const int32_t* flat = nullptr, const void* sigma1 = nullptr,
+                           int64_t stride_sigma1 = 0);
 int64_t qr_pushed_flag_offset(int dtype, int64_t I, int64_t n, int64_t batch);
 
 int64_t colgram_workspace_bytes(int dtype, int64_t rows, int64_t n, int64_t batch);
@@ -117,6 +118,7 @@ extern int g_qr_pair4;
 extern int g_eigh_big_occ;
 extern int g_sweep_stagger;
 extern int g_sweep_lean;
+extern int g_flat_pass;
 extern int g_rank_noise_c;
 extern int g_jacobi_live_wave;
 extern int g_eigh_small;

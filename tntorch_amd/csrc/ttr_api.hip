@@ -326,11 +326,11 @@ int ttr_qr_apply_pushed_gram(int dtype, int64_t k, int64_t I, int64_t n, int64_t
 
 int64_t ttr_eigh_workspace_bytes(int dtype, int64_t n, int64_t batch) { return eigh_workspace_bytes(dtype, n, batch); }
 
-int ttr_eigh_trunc(int dtype, int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts,
-                   int64_t stride_gpart, void* V, int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma,
-                   int32_t* info, int eig_mode, int use_delta, double delta2, const double* delta2_dev, int64_t rmax,
-                   int abs_floor, int32_t* sweeps, const int32_t* skip_items, const void* sigma_in, int64_t stride_sigma_in,
-                   void* workspace, int64_t workspace_bytes, void* stream) {
+static int eigh_trunc_checked(int dtype, int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts,
+                              int64_t stride_gpart, void* V, int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma,
+                              int32_t* info, int eig_mode, int use_delta, double delta2, const double* delta2_dev, int64_t rmax,
+                              int abs_floor, int32_t* sweeps, const int32_t* skip_items, const void* sigma_in,
+                              int64_t stride_sigma_in, void* workspace, int64_t workspace_bytes, void* stream, int skip_lean) {
   TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_eigh_trunc: bad dtype %d", dtype);
   TTR_REQUIRE(n >= 1 && batch >= 0 && rmax >= 1 && gparts >= 1, TTR_E_INVALID, "ttr_eigh_trunc: bad arguments");
   TTR_REQUIRE(abs_floor >= TTR_SOLVER_JACOBI_REL && abs_floor <= TTR_SOLVER_JACOBI_LIVE, TTR_E_INVALID,
@@ -341,7 +341,27 @@ int ttr_eigh_trunc(int dtype, int64_t n, int64_t batch, const void* G, int64_t l
               eig_mode);
   return eigh_dispatch(dtype, n, batch, G, ldg, strideG, gparts, stride_gpart, V, ldv, strideV, sigma, stride_sigma, info,
                        eig_mode, use_delta, delta2, rmax, abs_floor, sweeps, workspace, workspace_bytes,
-                       (hipStream_t)stream, delta2_dev, skip_items, sigma_in, stride_sigma_in);
+                       (hipStream_t)stream, delta2_dev, skip_items, sigma_in, stride_sigma_in, skip_lean);
+}
+
+int ttr_eigh_trunc(int dtype, int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts,
+                   int64_t stride_gpart, void* V, int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma,
+                   int32_t* info, int eig_mode, int use_delta, double delta2, const double* delta2_dev, int64_t rmax,
+                   int abs_floor, int32_t* sweeps, const int32_t* skip_items, const void* sigma_in, int64_t stride_sigma_in,
+                   void* workspace, int64_t workspace_bytes, void* stream) {
+  return eigh_trunc_checked(dtype, n, batch, G, ldg, strideG, gparts, stride_gpart, V, ldv, strideV, sigma, stride_sigma, info,
+                            eig_mode, use_delta, delta2, delta2_dev, rmax, abs_floor, sweeps, skip_items, sigma_in,
+                            stride_sigma_in, workspace, workspace_bytes, stream, 0);
+}
+
+int ttr_eigh_trunc_pass(int dtype, int64_t n, int64_t batch, const void* G, int64_t ldg, int64_t strideG, int64_t gparts,
+                        int64_t stride_gpart, void* V, int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma,
+                        int32_t* info, int eig_mode, int use_delta, double delta2, const double* delta2_dev, int64_t rmax,
+                        int abs_floor, int32_t* sweeps, const int32_t* skip_items, const void* sigma_in,
+                        int64_t stride_sigma_in, void* workspace, int64_t workspace_bytes, void* stream) {
+  return eigh_trunc_checked(dtype, n, batch, G, ldg, strideG, gparts, stride_gpart, V, ldv, strideV, sigma, stride_sigma, info,
+                            eig_mode, use_delta, delta2, delta2_dev, rmax, abs_floor, sweeps, skip_items, sigma_in,
+                            stride_sigma_in, workspace, workspace_bytes, stream, 1);
 }
 
 int ttr_eigh_top_ok(int64_t n, int64_t r) { return n >= 40 && n <= 64 && r >= 1 && r <= 32 && r < n; }
@@ -476,17 +496,28 @@ int ttr_tridiag_back(int dtype, int64_t n, int64_t batch, int64_t k, const void*
   return tridiag_back_dispatch(dtype, n, batch, k, A, lda, strideA, tau, Z, (hipStream_t)stream);
 }
 
-int ttr_project(int dtype, int64_t R, int64_t n, int64_t ro, int64_t batch, const void* M, int64_t ldm, int64_t strideM,
-                const void* V1, int64_t ldv1, int64_t strideV1, const void* V2, int64_t ldv2, int64_t strideV2,
-                const void* sigma, int64_t stride_sigma, int scale_right, void* right, int64_t ldr, int64_t strideR,
-                void* left, int64_t ldl, int64_t strideL, const int32_t* rows32, void* stream) {
+int ttr_project_flat(int dtype, int64_t R, int64_t n, int64_t ro, int64_t batch, const void* M, int64_t ldm, int64_t strideM,
+                     const void* V1, int64_t ldv1, int64_t strideV1, const void* V2, int64_t ldv2, int64_t strideV2,
+                     const void* sigma, int64_t stride_sigma, int scale_right, void* right, int64_t ldr, int64_t strideR,
+                     void* left, int64_t ldl, int64_t strideL, const int32_t* rows32, const int32_t* flat, const void* sigma1,
+                     int64_t stride_sigma1, void* stream) {
   TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_project: bad dtype %d", dtype);
   TTR_REQUIRE(R >= 1 && n >= 1 && ro >= 1 && batch >= 0, TTR_E_INVALID, "ttr_project: bad shape");
   if (batch == 0) return TTR_OK;
   TTR_REQUIRE(M && V2 && right, TTR_E_INVALID, "ttr_project: null pointer");
   TTR_REQUIRE(!scale_right || sigma, TTR_E_INVALID, "ttr_project: scale_right needs sigma");
+  TTR_REQUIRE(!flat || !V1 || sigma1, TTR_E_INVALID, "ttr_project_flat: flat needs sigma1");
   return sweep_project_dispatch(dtype, R, n, ro, batch, M, ldm, strideM, V1, ldv1, strideV1, V2, ldv2, strideV2, sigma,
-                                stride_sigma, scale_right, right, ldr, strideR, left, ldl, strideL, (hipStream_t)stream, rows32);
+                                stride_sigma, scale_right, right, ldr, strideR, left, ldl, strideL, (hipStream_t)stream, rows32,
+                                flat, sigma1, stride_sigma1);
+}
+
+int ttr_project(int dtype, int64_t R, int64_t n, int64_t ro, int64_t batch, const void* M, int64_t ldm, int64_t strideM,
+                const void* V1, int64_t ldv1, int64_t strideV1, const void* V2, int64_t ldv2, int64_t strideV2,
+                const void* sigma, int64_t stride_sigma, int scale_right, void* right, int64_t ldr, int64_t strideR,
+                void* left, int64_t ldl, int64_t strideL, const int32_t* rows32, void* stream) {
+  return ttr_project_flat(dtype, R, n, ro, batch, M, ldm, strideM, V1, ldv1, strideV1, V2, ldv2, strideV2, sigma, stride_sigma,
+                          scale_right, right, ldr, strideR, left, ldl, strideL, rows32, nullptr, nullptr, 0, stream);
 }
 
 int64_t ttr_colgram_workspace_bytes(int dtype, int64_t rows, int64_t n, int64_t batch) {
@@ -568,6 +599,10 @@ int ttr_debug_set_knob(int knob, int value) {
     case TTR_KNOB_SWEEP_STAGGER:
       TTR_REQUIRE(value >= 0 && value <= 2, TTR_E_INVALID, "ttr_debug_set_knob: stagger mode %d outside [0, 2]", value);
       g_sweep_stagger = value;
+      return TTR_OK;
+    case TTR_KNOB_FLAT_PASS:
+      TTR_REQUIRE(value >= 0 && value <= 1, TTR_E_INVALID, "ttr_debug_set_knob: flat pass-through switch %d outside [0, 1]", value);
+      g_flat_pass = value;
       return TTR_OK;
     case TTR_KNOB_SWEEP_LEAN:
       TTR_REQUIRE(value >= 0 && value <= 1, TTR_E_INVALID, "ttr_debug_set_knob: lean sweep switch %d outside [0, 1]", value);

@@ -65,6 +65,9 @@ struct EighArgs {
   const int32_t* skip_items;
   const T* sigma_in;
   int64_t stride_sigma_in;
+  // != 0 (ttr_eigh_trunc_pass, TTR_KNOB_FLAT_PASS): the caller takes a pass-through item's eigenvectors as the identity without
+  // reading them (ttr_project's `flat`) -- V is not written for it; sigma, info and sweeps are
+  int skip_lean;
   // eigh_tridiag_kernel<T, true>: top_r largest eigenpairs by the top-r path when the kept spectrum is flat within top_thr and has
   // no close pair (top_flat[b] = 1, optional), the QL phase otherwise (top_flat[b] = 0)
   int32_t* top_flat;
@@ -119,10 +122,12 @@ __global__ __launch_bounds__(NTH) void eigh_jacobi_kernel(EighArgs<T> p) {
   const int nf = p.n;
   if (p.skip_items && p.skip_items[bt] != 0) {  // (block-uniform) pass-through item, see EighArgs
     const int n = nf;
-    T* __restrict__ Vo = p.V + bt * p.strideV;
-    for (int idx = tid; idx < n * n; idx += NTH) {
-      const int i = idx / n, j = idx - i * n;
-      Vo[(int64_t)i * p.ldv + j] = (i == j) ? T(1) : T(0);
+    if (!p.skip_lean) {
+      T* __restrict__ Vo = p.V + bt * p.strideV;
+      for (int idx = tid; idx < n * n; idx += NTH) {
+        const int i = idx / n, j = idx - i * n;
+        Vo[(int64_t)i * p.ldv + j] = (i == j) ? T(1) : T(0);
+      }
     }
     const T* __restrict__ si = p.sigma_in + bt * p.stride_sigma_in;
     for (int i = tid; i < n; i += NTH) p.sigma[bt * p.stride_sigma + i] = si[i];
@@ -1684,7 +1689,8 @@ static int eigh_typed(int dtype, int64_t n, int64_t batch, const void* G, int64_
                       int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma, int32_t* info, int eig_mode,
                       int use_delta, double delta2, int64_t rmax, int abs_floor, int32_t* sweeps, void* ws,
                       int64_t ws_bytes, hipStream_t stream, const double* delta2_dev = nullptr,
-                      const int32_t* skip_items = nullptr, const void* sigma_in = nullptr, int64_t stride_sigma_in = 0) {
+                      const int32_t* skip_items = nullptr, const void* sigma_in = nullptr, int64_t stride_sigma_in = 0,
+                      int skip_lean = 0) {
   const int64_t nmax = eigh_max_n(dtype);
   TTR_REQUIRE(n >= 1 && n <= nmax, TTR_E_UNSUPPORTED, "ttr_eigh_trunc: n = %lld outside [1, %lld]", (long long)n,
               (long long)nmax);
@@ -1692,6 +1698,7 @@ static int eigh_typed(int dtype, int64_t n, int64_t batch, const void* G, int64_
   p.delta2_dev = delta2_dev;
   p.noise_c = g_rank_noise_c;
   p.skip_items = skip_items; p.sigma_in = (const T*)sigma_in; p.stride_sigma_in = stride_sigma_in;
+  p.skip_lean = (skip_lean && g_flat_pass) ? 1 : 0;   // (TTR_KNOB_FLAT_PASS = 0: pass-through items write V = I all the same)
   TTR_REQUIRE(!skip_items || (sigma_in && !(abs_floor == TTR_SOLVER_TRIDIAG && n <= 64)), TTR_E_INVALID,
               "ttr_eigh_trunc: skip_items needs sigma_in and a Jacobi solver");
   p.n = (int)n;
@@ -1751,14 +1758,14 @@ int eigh_dispatch(int dtype, int64_t n, int64_t batch, const void* G, int64_t ld
                   int64_t ldv, int64_t strideV, void* sigma, int64_t stride_sigma, int32_t* info, int eig_mode,
                   int use_delta, double delta2, int64_t rmax, int abs_floor, int32_t* sweeps, void* ws,
                   int64_t ws_bytes, hipStream_t stream, const double* delta2_dev, const int32_t* skip_items,
-                  const void* sigma_in, int64_t stride_sigma_in) {
+                  const void* sigma_in, int64_t stride_sigma_in, int skip_lean) {
   if (dtype == TTR_F32)
     return eigh_typed<float>(dtype, n, batch, G, ldg, strideG, gparts, stride_gpart, V, ldv, strideV, sigma, stride_sigma, info, eig_mode,
                              use_delta, delta2, rmax, abs_floor, sweeps, ws, ws_bytes, stream, delta2_dev, skip_items, sigma_in,
-                             stride_sigma_in);
+                             stride_sigma_in, skip_lean);
   return eigh_typed<double>(dtype, n, batch, G, ldg, strideG, gparts, stride_gpart, V, ldv, strideV, sigma, stride_sigma, info, eig_mode,
                             use_delta, delta2, rmax, abs_floor, sweeps, ws, ws_bytes, stream, delta2_dev, skip_items, sigma_in,
-                            stride_sigma_in);
+                            stride_sigma_in, skip_lean);
 }
 
 // pass 1 of a batch-mode bond, n <= 64: the r largest eigenpairs (flat[b] = 1) or the full QL decomposition (flat[b] = 0) per item

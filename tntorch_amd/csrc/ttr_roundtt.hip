@@ -335,6 +335,7 @@ int ttr_round_tt(int dtype, int64_t N, const int64_t* shapes, int64_t batch, con
     const int64_t rmax_rule = rcap_mu < 1 ? 1 : (rcap_mu > kNoCap ? kNoCap : rcap_mu);
     TTR_TRY(ttr_rowgram(dt, R, n, B, M, n, R * n, G, parts, r32, st));
     const void* V1p = nullptr;
+    const int32_t* pflat = nullptr;   // the pass-through flags, where pass 2 took them
     if (svd) {
       const int32_t* flat = nullptr;
       // r of the top-r launch: the cap in batch mode (only with a cap), min(cap, 32) in eps mode (see _hipops.truncate)
@@ -356,10 +357,12 @@ int ttr_round_tt(int dtype, int64_t N, const int64_t* shapes, int64_t batch, con
         }
       }
       TTR_TRY(ttr_rotgram(dt, R, n, B, M, n, R * n, V1, R, R * R, G2, parts, flat, r32, st));
-      TTR_TRY(ttr_eigh_trunc(dt, R, B, G2, R, parts * R * R, parts, R * R, V, R, R * R, sig, R, info, TTR_EIG_RAW, eps_mode ? 1 : 0, 0.0,
-                             d2dev, rmax_rule, TTR_SOLVER_JACOBI_LIVE, nullptr, flat, flat ? sig1 : nullptr, flat ? R : 0, eigws,
-                             p.eig_wsb, st));
+      // (pass-through items: V is not written -- ttr_project_flat below takes the same flags and does not read it)
+      TTR_TRY(ttr_eigh_trunc_pass(dt, R, B, G2, R, parts * R * R, parts, R * R, V, R, R * R, sig, R, info, TTR_EIG_RAW, eps_mode ? 1 : 0,
+                                  0.0, d2dev, rmax_rule, TTR_SOLVER_JACOBI_LIVE, nullptr, flat, flat ? sig1 : nullptr, flat ? R : 0,
+                                  eigws, p.eig_wsb, st));
       V1p = V1;
+      pflat = flat;
     } else {
       TTR_TRY(ttr_eigh_trunc(dt, R, B, G, R, parts * R * R, parts, R * R, V, R, R * R, sig, R, info, TTR_EIG_REF, eps_mode ? 1 : 0, 0.0,
                              d2dev, rmax_rule, TTR_SOLVER_TRIDIAG, nullptr, nullptr, nullptr, 0, eigws, p.eig_wsb, st));
@@ -374,8 +377,8 @@ int ttr_round_tt(int dtype, int64_t N, const int64_t* shapes, int64_t batch, con
     }
     void* lnew = ws + p.off_left[lslot];
     lslot = (lslot + 1) % 3;
-    TTR_TRY(ttr_project(dt, R, n, cap, B, M, n, R * n, V1p, R, R * R, V, R, R * R, sig, R, 1, cores_out[mu], n, cap * n, lnew, cap,
-                        R * cap, r32, st));
+    TTR_TRY(ttr_project_flat(dt, R, n, cap, B, M, n, R * n, V1p, R, R * R, V, R, R * R, sig, R, 1, cores_out[mu], n, cap * n, lnew, cap,
+                             R * cap, r32, pflat, pflat ? sig1 : nullptr, pflat ? R : 0, st));
     if (svd)
       TTR_TRY(ttr_orth_fixup(dt, cap, n, B, cores_out[mu], n, 1, cap * n, sig, R, (double)R * epsT, eps_mode ? info : nullptr,
                              p.orth_wsb > 0 ? (void*)(ws + p.off_orth) : nullptr, p.orth_wsb, st));

@@ -48,7 +48,16 @@ struct SweepArgs {
   T* left;          // R x ro (nullable)
   int64_t ldl, strideL;
   int stagger;      // TTR_KNOB_SWEEP_STAGGER: 0 = columns in order, 1 = project staggered per item, 2 = the Gram kernels as well
+  // project, pass-through items of the two-pass truncation (TTR_KNOB_FLAT_PASS; nullptr: none): flat[b] != 0 -> this item's V2 is
+  // the identity and its sigma is pass 1's, neither of which is loaded: U = V1[:, :ro], scales from sigma1 (needs V1)
+  const int32_t* flat;
+  const T* sigma1;
+  int64_t stride_sigma1;
 };
+
+// One entry of V1 as the product V1 I leaves it in an MFMA accumulator that started at +0: the value itself, and +0 for -0.
+template <typename T>
+__device__ __forceinline__ T times_identity(T x) { return x + T(0); }
 
 __host__ __device__ inline void split_range(int64_t chunks, int nsplit, int split, int64_t& c0, int64_t& c1) {
   const int64_t per = (chunks + nsplit - 1) / nsplit;
@@ -238,12 +247,16 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_ke
   const int R = p.R, ro = p.ro;
   const int nt = (ro + 15) / 16;
   const T* __restrict__ V2 = p.V2 + b * p.strideV2;
-  const T* __restrict__ sg = p.sigma ? p.sigma + b * p.stride_sigma : nullptr;
+  // (block-uniform, decided once ahead of every load) pass-through item: V2 = I and sigma = sigma1, see SweepArgs::flat
+  const bool flat = p.flat && p.V1 && p.flat[b] != 0;
+  const T* __restrict__ sg = flat ? p.sigma1 + b * p.stride_sigma1 : (p.sigma ? p.sigma + b * p.stride_sigma : nullptr);
   T* __restrict__ Lo = (p.left && split == 0) ? p.left + b * p.strideL : nullptr;
   // ---- prologue: U = V1 V2[:, :ro] on the matrix cores (or U = V2[:, :ro]); split 0 also emits left = U diag(sigma)
-  for (int idx = tid; idx < 64 * 64; idx += kThreads) {
-    const int m = idx >> 6, i = idx & 63;
-    V2l[m * V2LD + i] = (m < R && i < ro) ? V2[(int64_t)m * p.ldv2 + i] : T(0);
+  if (!flat) {
+    for (int idx = tid; idx < 64 * 64; idx += kThreads) {
+      const int m = idx >> 6, i = idx & 63;
+      V2l[m * V2LD + i] = (m < R && i < ro) ? V2[(int64_t)m * p.ldv2 + i] : T(0);
+    }
   }
   if (tid < 64) {
     T sc = T(1);
@@ -253,7 +266,13 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? 4 : 1)) void project_ke
     }
     isg[tid] = sc;
   }
-  if (p.V1) {
+  if (flat) {  // U = V1[:, :ro], what the product with the identity gives: straight into the image
+    const T* __restrict__ V1 = p.V1 + b * p.strideV1;
+    for (int idx = tid; idx < 64 * 64; idx += kThreads) {
+      const int k = idx >> 6, i = idx & 63;
+      Ul[urow(k) + i] = (k < R && i < ro) ? times_identity(V1[(int64_t)k * p.ldv1 + i]) : T(0);
+    }
+  } else if (p.V1) {
     const T* __restrict__ V1 = p.V1 + b * p.strideV1;
     for (int idx = tid; idx < 64 * 64; idx += kThreads) {
       const int k = idx >> 6, m = idx & 63;
@@ -514,13 +533,23 @@ __global__ __launch_bounds__(kThreads, 8) void project_rows32_kernel(SweepArgs<T
   const int ro = p.ro;           // <= 32, R = 64 (project_typed)
   const int nt = (ro + 15) / 16;
   const T* __restrict__ V2 = p.V2 + b * p.strideV2;
-  const T* __restrict__ sg = p.sigma ? p.sigma + b * p.stride_sigma : nullptr;
+  const bool flat = p.flat && p.V1 && p.flat[b] != 0;  // (block-uniform, ahead of every load) as in project_kernel
+  const T* __restrict__ sg = flat ? p.sigma1 + b * p.stride_sigma1 : (p.sigma ? p.sigma + b * p.stride_sigma : nullptr);
   T* __restrict__ Lo = (p.left && split == 0) ? p.left + b * p.strideL : nullptr;
   // ---- prologue: the sums of project_kernel's in the same order.  V1 is not staged: wave w reads ITS 16 rows straight from global
   // memory as the A operand (lane (g, cl), K step ks <-> V1[16 w + cl][4 ks + g]), and U replaces V2 in the one image.
-  for (int idx = tid; idx < 64 * 32; idx += kThreads) {
-    const int m = idx >> 5, i = idx & 31;
-    Wl[m * ULD + i] = (i < ro) ? V2[(int64_t)m * p.ldv2 + i] : T(0);
+  // A pass-through item's image is V1[:, :ro] itself.
+  if (flat) {
+    const T* __restrict__ V1 = p.V1 + b * p.strideV1;
+    for (int idx = tid; idx < 64 * 32; idx += kThreads) {
+      const int k = idx >> 5, i = idx & 31;
+      Wl[k * ULD + i] = (i < ro) ? times_identity(V1[(int64_t)k * p.ldv1 + i]) : T(0);
+    }
+  } else {
+    for (int idx = tid; idx < 64 * 32; idx += kThreads) {
+      const int m = idx >> 5, i = idx & 31;
+      Wl[m * ULD + i] = (i < ro) ? V2[(int64_t)m * p.ldv2 + i] : T(0);
+    }
   }
   if (tid < 32) {
     T sc = T(1);
@@ -530,7 +559,7 @@ __global__ __launch_bounds__(kThreads, 8) void project_rows32_kernel(SweepArgs<T
     }
     isg[tid] = sc;
   }
-  if (p.V1) {
+  if (p.V1 && !flat) {
     const T* __restrict__ V1 = p.V1 + b * p.strideV1 + (int64_t)(16 * wave + cl) * p.ldv1 + g;
     T a[16];
 #pragma unroll
@@ -1017,6 +1046,7 @@ int colproject_dispatch(int dtype, int64_t rows, int64_t n, int64_t ro, int64_t 
 
 int g_sweep_stagger = 1;   // ttr_debug_set_knob(TTR_KNOB_SWEEP_STAGGER)
 int g_sweep_lean = 1;      // ttr_debug_set_knob(TTR_KNOB_SWEEP_LEAN)
+int g_flat_pass = 1;       // ttr_debug_set_knob(TTR_KNOB_FLAT_PASS): 0 = pass-through items take the identity round trip (A/B)
 // launches of fewer items run the generic instance alone (latency-bound sizes: a second launch costs more than the build gains)
 constexpr int64_t kLeanMinItems = 256;
 
@@ -1091,9 +1121,13 @@ template <typename T>
 static int project_typed(int64_t R, int64_t n, int64_t ro, int64_t batch, const void* Mx, int64_t ldm, int64_t strideM,
                          const void* V1, int64_t ldv1, int64_t strideV1, const void* V2, int64_t ldv2, int64_t strideV2,
                          const void* sigma, int64_t stride_sigma, int scale_right, void* right, int64_t ldr,
-                         int64_t strideR, void* left, int64_t ldl, int64_t strideL, hipStream_t stream, const int32_t* rows32) {
+                         int64_t strideR, void* left, int64_t ldl, int64_t strideL, hipStream_t stream, const int32_t* rows32,
+                         const int32_t* flat, const void* sigma1, int64_t stride_sigma1) {
   SweepArgs<T> p{};
   p.rows32 = rows32;
+  if (g_flat_pass && flat && V1) {   // (TTR_KNOB_FLAT_PASS = 0: the flags are ignored -- every item loads its V2 and sigma)
+    p.flat = flat; p.sigma1 = (const T*)sigma1; p.stride_sigma1 = stride_sigma1;
+  }
   p.R = (int)R; p.n = n; p.M = (const T*)Mx; p.ldm = ldm; p.strideM = strideM;
   p.V1 = (const T*)V1; p.ldv1 = ldv1; p.strideV1 = strideV1;
   p.V2 = (const T*)V2; p.ldv2 = ldv2; p.strideV2 = strideV2;
@@ -1119,6 +1153,7 @@ static int project_typed(int64_t R, int64_t n, int64_t ro, int64_t batch, const 
     q.right = p.right + b0 * strideR;
     if (left) q.left = p.left + b0 * strideL;
     if (rows32) q.rows32 = rows32 + b0;
+    if (p.flat) { q.flat = p.flat + b0; q.sigma1 = p.sigma1 + b0 * stride_sigma1; }
     const dim3 grid((unsigned)p.nsplit, (unsigned)nb);
     bool two = false;
     if constexpr (std::is_same<T, float>::value) {   // two instances, as in gram_typed
@@ -1138,14 +1173,16 @@ int sweep_project_dispatch(int dtype, int64_t R, int64_t n, int64_t ro, int64_t 
                            int64_t strideM, const void* V1, int64_t ldv1, int64_t strideV1, const void* V2, int64_t ldv2,
                            int64_t strideV2, const void* sigma, int64_t stride_sigma, int scale_right, void* right,
                            int64_t ldr, int64_t strideR, void* left, int64_t ldl, int64_t strideL, hipStream_t stream,
-                           const int32_t* rows32) {
+                           const int32_t* rows32, const int32_t* flat, const void* sigma1, int64_t stride_sigma1) {
   TTR_REQUIRE(R >= 1 && R <= 64 && ro >= 1 && ro <= R, TTR_E_UNSUPPORTED,
               "ttr_project: %lld rows / %lld kept (the fused kernel holds <= 64 rows)", (long long)R, (long long)ro);
   if (dtype == TTR_F32)
     return project_typed<float>(R, n, ro, batch, Mx, ldm, strideM, V1, ldv1, strideV1, V2, ldv2, strideV2, sigma,
-                                stride_sigma, scale_right, right, ldr, strideR, left, ldl, strideL, stream, rows32);
+                                stride_sigma, scale_right, right, ldr, strideR, left, ldl, strideL, stream, rows32, flat, sigma1,
+                                stride_sigma1);
   return project_typed<double>(R, n, ro, batch, Mx, ldm, strideM, V1, ldv1, strideV1, V2, ldv2, strideV2, sigma,
-                               stride_sigma, scale_right, right, ldr, strideR, left, ldl, strideL, stream, rows32);
+                               stride_sigma, scale_right, right, ldr, strideR, left, ldl, strideL, stream, rows32, flat, sigma1,
+                                stride_sigma1);
 }
 
 }  // namespace ttr
