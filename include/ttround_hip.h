@@ -59,7 +59,8 @@ extern "C" {
    ttr_ttm_grad_core, and ttr_ttm_lookup_workspace_bytes and ttr_ttm_lookup_step, and ttr_core_compose, and ttr_env_half_apply, and ttr_ritz_parts, ttr_ritz_workspace_bytes, ttr_ritz_gram and
    ttr_ritz_update, and ttr_ttm_lookup_grad_core_slab_rows, ttr_ttm_lookup_grad_core_workspace_bytes, ttr_ttm_lookup_grad_core,
    ttr_ttm_lookup_grad_input_workspace_bytes, ttr_ttm_lookup_grad_input and ttr_segment_sum, and ttr_eigh_trunc_pass and
-   ttr_project_flat (+ TTR_KNOB_FLAT_PASS; ttr_eigh_trunc and ttr_project keep their signatures and behaviour).  ttr_version() returns the value the library was built with; the Python
+   ttr_project_flat (+ TTR_KNOB_FLAT_PASS; ttr_eigh_trunc and ttr_project keep their signatures and behaviour), and ttr_cg_parts,
+   ttr_cg_workspace_bytes, ttr_cg_dot, ttr_cg_update and ttr_cg_direction.  ttr_version() returns the value the library was built with; the Python
    binding refuses to use a library whose version differs (a stale .so would take misaligned arguments silently). */
 #define TTR_ABI_VERSION 17
 int ttr_version(void);
@@ -1456,6 +1457,57 @@ int ttr_ritz_gram(int dtype, int mode, int64_t n, const void* X, const void* AX,
                   const void* AP, double* part, int64_t workspace_bytes, void* stream);
 int ttr_ritz_update(int dtype, int mode, int which, int first, int64_t n, double rel, const double* part, void* X, void* AX, void* W,
                     const void* AW, void* P, void* AP, double* state, double* sweep, void* stream);
+
+/*
+ * One conjugate-gradient step in three launches, the local solver of the rank-adaptive AMEn solver (added under ABI 17;
+ * ttamen.py `tt_amen_solve`; ttsolve.py `_cg` is the specification of the recurrences).  The state of a local
+ * system B x = f is four contiguous vectors of n elements in the dtype: the iterate v, the residual r, the direction p and
+ * Bp = B p (the caller's matvec, between ttr_cg_direction of one step and ttr_cg_dot of the next).  None of the vectors of one
+ * call may overlap another.  Step s (`step`, counted from 0; only its parity is used) is
+ *     pBp = p . Bp;  active = rs > thr2;  good = pBp > 0;  live = active & good;  alpha = live ? rs / pBp : 0
+ *     v += alpha p;  r -= alpha Bp;  rs' = r . r;  beta = live ? rs' / max(rs, tiny) : 0;  p = r + beta p;  rs <- rs'
+ * with tiny the smallest normal number of the dtype.  A step that is not live (frozen: rs <= thr2, or pBp <= 0) writes NO vector
+ * and carries rs over.
+ *
+ * state, fp64[8], the caller's, set before step 0 to (rs, anything, thr2, 0, ...):
+ *     [0], [1]   rs: step s reads slot s & 1, its ttr_cg_direction writes slot 1 - (s & 1), which step s + 1 reads
+ *     [2]        thr2 = rel^2 f . f: read, never written
+ *     [3]        += 1 per step with rs > thr2 and pBp <= 0 (a lost positive definiteness): read and written by one thread
+ *     [4] .. [6] live (1 or 0), alpha and pBp of the last ttr_cg_update
+ *     [7]        beta of the last ttr_cg_direction
+ * No launch reads a word that another workgroup of the same launch writes: ttr_cg_update reads [s & 1] and [2] and writes
+ * [3] .. [6]; ttr_cg_direction reads [s & 1] and [4] and writes [1 - (s & 1)] and [7].  All scalars stay on the device.
+ *
+ * ttr_cg_parts / ttr_cg_workspace_bytes: the number of workgroups of each of the three launches, the rule of ttr_ritz_parts
+ * (1 + (ceil(n / V) - 1) / 1024 capped at TTR_CG_MAX_PARTS, V = 16 bytes / element size), and the bytes of `part`, two rows of
+ * `parts` doubles (row 0: the shares of p . Bp, row 1: of r . r).  Both are functions of n and the dtype alone.  TTR_E_INVALID
+ * (negative) for a bad dtype or n < 1.
+ *
+ * ttr_cg_dot: part[0][g] = workgroup g's share of p . Bp.  Products and sums in double, one fma per product; 16-byte packs where
+ * both pointers are 16-byte aligned, element loads with the same arithmetic otherwise and for the last pack of an n that is no
+ * multiple of V.  Pack q belongs to thread q % 256 of workgroup (q / 256) % parts, which adds its packs in increasing q; lanes
+ * meet in the library's wave sum, the four waves in increasing order.
+ * ttr_cg_update: every workgroup adds part[0][*] in increasing g (the previous launch's reduction, finished in this one's
+ * prologue), forms alpha in double, and updates its slice of v and r in place: evaluated in double (one fma), rounded once, every
+ * element read and written by the same thread.  It writes its share of r . r, of the ROUNDED r, to part[1][g] (a step that is
+ * not live: zeros).  The first thread of workgroup 0 writes state[3] .. [6].
+ * ttr_cg_direction: every workgroup adds part[1][*] in increasing g, forms beta, and writes its slice of p = r + beta p; the first
+ * thread of workgroup 0 stores the next rs (rs' of a live step, rs otherwise) and beta.
+ * The same call gives the same bits, from aligned pointers and from pointers offset by an element.  No atomics, no
+ * grid-wide synchronisation, nothing read back, no workspace beyond `part` and `state`.
+ *
+ * Before any launch: TTR_E_INVALID for a bad dtype, n < 1, step < 0, a null pointer, or two vectors of the call that share a
+ * byte; TTR_E_WORKSPACE for workspace_bytes below ttr_cg_workspace_bytes; TTR_E_UNSUPPORTED for n of 2^57 or more.
+ * Profiling kind: TTR_PROF_MISC.
+ */
+#define TTR_CG_MAX_PARTS 256
+int ttr_cg_parts(int dtype, int64_t n);
+int64_t ttr_cg_workspace_bytes(int dtype, int64_t n);
+int ttr_cg_dot(int dtype, int64_t n, const void* p, const void* Bp, double* part, int64_t workspace_bytes, void* stream);
+int ttr_cg_update(int dtype, int step, int64_t n, const void* p, const void* Bp, void* v, void* r, double* part,
+                  int64_t workspace_bytes, double* state, void* stream);
+int ttr_cg_direction(int dtype, int step, int64_t n, const void* r, void* p, const double* part, int64_t workspace_bytes,
+                     double* state, void* stream);
 
 #ifdef __cplusplus
 }

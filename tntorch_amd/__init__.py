@@ -19,7 +19,8 @@ and drawing index vectors from a train read as an unnormalised mass function: ``
 ``matrix.py`` with their products with a batch of vectors: ``tn.TTMatrix``, ``tn.CPMatrix``, ``tn.tt_multiply``, ``tn.cp_multiply``, and a batch of rows of a TT-matrix
 (``tn.tt_lookup``: the embedding table; ``tn.tt_embedding`` / ``tn.tt_embedding_bag``: the same table, trainable on the device), and the products that stay in TT format (``tn.tt_apply``: a TT-matrix applied to a
 train, ``tn.tt_matmul``, ``tn.tt_transpose``), and the solver that inverts them: ``tn.tt_solve``, fixed-rank ALS for ``A x = b``
-with a symmetric positive definite ``TTMatrix`` and a train ``b`` (the three-layer environment fused into one kernel), and the extreme
+with a symmetric positive definite ``TTMatrix`` and a train ``b`` (the three-layer environment fused into one kernel), and
+``tn.tt_amen_solve``, the same system at ranks that adapt while the sweeps run (AMEn; the local CG steps are three fused kernels), and the extreme
 eigenpair of a symmetric ``TTMatrix``: ``tn.tt_eigsh``, fixed-rank ALS whose local LOBPCG steps are two fused kernels, and gradient-based fitting (``autodiff.py``):
 ``tn.optimize`` and ``tn.dof``, with ``t[X]`` at index arrays, ``Tensor.torch()``, ``tn.dist`` / ``tn.relative_error`` against a
 dense tensor and ``tn.tt_multiply`` (in the cores and the tensor) differentiable on the device (hand-written backward passes; every other operation refuses device cores that require
@@ -37,6 +38,7 @@ from .embedding import *  # noqa: F401,F403
 from .ttalgebra import *  # noqa: F401,F403
 from .ttsolve import *  # noqa: F401,F403
 from .tteigs import *  # noqa: F401,F403
+from .ttamen import *  # noqa: F401,F403
 from .maxvol import *  # noqa: F401,F403
 from .cross import *  # noqa: F401,F403
 from .ops import *  # noqa: F401,F403
@@ -46,7 +48,7 @@ from .automata import *  # noqa: F401,F403
 from .logic import *  # noqa: F401,F403
 from .anova import *  # noqa: F401,F403
 from .autodiff import *  # noqa: F401,F403
-from . import autodiff, automata, embedding, logic, lookup, tteigs, ttsolve  # noqa: F401
+from . import autodiff, automata, embedding, logic, lookup, ttamen, tteigs, ttsolve  # noqa: F401
 from . import dist_batch  # noqa: F401
 from ._patch import patch  # noqa: F401
 

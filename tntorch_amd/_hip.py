@@ -1984,3 +1984,61 @@ def ritz_update(mode: int, which: int, first: int, rel: float, part: torch.Tenso
             raise ValueError("ritz_update: state and sweep must be contiguous fp64 device tensors of 8 and 4 elements")
     _call("ttr_ritz_update", dt, int(mode), int(which), int(first), n, float(rel), part.data_ptr(), X.data_ptr(), AX.data_ptr(),
           W.data_ptr(), _ptr(AW), _ptr(P), _ptr(AP), state.data_ptr(), sweep.data_ptr())
+
+
+def cg_parts(dt: torch.dtype, n: int) -> int:
+    """ttr_cg_parts: the workgroups of each launch of a CG step on vectors of n elements, a function of n and the dtype alone."""
+    parts = int(lib().ttr_cg_parts(dtype_code(dt), int(n)))
+    if parts < 0:
+        _check(parts, "ttr_cg_parts")
+    return parts
+
+
+def cg_workspace_bytes(dt: torch.dtype, n: int) -> int:
+    """ttr_cg_workspace_bytes: the bytes of ``part``, two rows of ``cg_parts`` doubles."""
+    wsb = int(lib().ttr_cg_workspace_bytes(dtype_code(dt), int(n)))
+    if wsb < 0:
+        _check(wsb, "ttr_cg_workspace_bytes")
+    return wsb
+
+
+def _cg_operands(who: str, vecs, part: torch.Tensor, state: Optional[torch.Tensor]) -> int:
+    """The length of the contiguous device vectors ``vecs`` of one dtype; ``part`` and ``state`` are contiguous fp64 tensors on
+    their device (the library checks the size of ``part``), ``state`` of 8 elements."""
+    x = vecs[0]
+    if not (x.is_cuda and x.dim() == 1 and x.is_contiguous()):
+        raise ValueError("{}: the vectors must be contiguous device vectors".format(who))
+    for v in vecs[1:]:
+        if not (v.shape == x.shape and v.dtype == x.dtype and v.device == x.device and v.is_contiguous()):
+            raise ValueError("{}: the vectors must be contiguous, of one length and dtype and on one device".format(who))
+    for t, k in ((part, None), (state, 8)):
+        if t is not None and not (t.dtype == torch.float64 and t.is_contiguous() and t.device == x.device
+                                  and (k is None or t.numel() == k)):
+            raise ValueError("{}: part and state must be contiguous fp64 tensors on the vectors' device, state of 8 elements".format(who))
+    return int(x.numel())
+
+
+@_on_device
+def cg_dot(p: torch.Tensor, Bp: torch.Tensor, part: torch.Tensor) -> None:
+    """ttr_cg_dot: row 0 of ``part`` (fp64 [2, cg_parts]) receives the workgroups' shares of p . Bp."""
+    n = _cg_operands("cg_dot", (p, Bp), part, None)
+    _call("ttr_cg_dot", dtype_code(p.dtype), n, p.data_ptr(), Bp.data_ptr(), part.data_ptr(), int(part.numel()) * 8)
+
+
+@_on_device
+def cg_update(step: int, p: torch.Tensor, Bp: torch.Tensor, v: torch.Tensor, r: torch.Tensor, part: torch.Tensor,
+              state: torch.Tensor) -> None:
+    """ttr_cg_update, in place: finishes p . Bp from row 0 of ``part``, forms alpha from ``state`` (fp64[8]) on the device,
+    v += alpha p, r -= alpha Bp, and the shares of r . r go to row 1.  Nothing is read back.  See include/ttround_hip.h."""
+    n = _cg_operands("cg_update", (p, Bp, v, r), part, state)
+    _call("ttr_cg_update", dtype_code(p.dtype), int(step), n, p.data_ptr(), Bp.data_ptr(), v.data_ptr(), r.data_ptr(),
+          part.data_ptr(), int(part.numel()) * 8, state.data_ptr())
+
+
+@_on_device
+def cg_direction(step: int, r: torch.Tensor, p: torch.Tensor, part: torch.Tensor, state: torch.Tensor) -> None:
+    """ttr_cg_direction, in place: finishes r . r from row 1 of ``part``, forms beta, p = r + beta p, and stores the next rs in
+    ``state``."""
+    n = _cg_operands("cg_direction", (r, p), part, state)
+    _call("ttr_cg_direction", dtype_code(p.dtype), int(step), n, r.data_ptr(), p.data_ptr(), part.data_ptr(), int(part.numel()) * 8,
+          state.data_ptr())

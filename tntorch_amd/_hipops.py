@@ -2419,3 +2419,38 @@ def ritz_update(mode: int, which: int, first: int, rel: float, part: torch.Tenso
                 sweep: torch.Tensor) -> None:
     """The Rayleigh-Ritz step on the six vectors, in place: one launch of ttr_ritz_update."""
     _hip.ritz_update(mode, which, first, rel, part, X, AX, W, AW, P, AP, state, sweep)
+
+
+# ---------------------------------------------------------------------------------------------- tt_amen_solve (ttamen.py; DESIGN section 32)
+cg_parts = _hip.cg_parts
+cg_workspace_bytes = _hip.cg_workspace_bytes
+cg_dot = _hip.cg_dot
+cg_update = _hip.cg_update
+cg_direction = _hip.cg_direction
+
+
+def cg_solve(Phi: torch.Tensor, Ak: torch.Tensor, Psi: torch.Tensor, f: torch.Tensor, x0: torch.Tensor, rel: float, iters: int,
+             stat: torch.Tensor) -> torch.Tensor:
+    """``iters`` steps of conjugate gradients on B v = f from x0, down to ||r|| <= rel ||f||, with no readback: ``ttsolve._cg``
+    with its vector and scalar ops on ttr_cg_dot / ttr_cg_update / ttr_cg_direction, three launches between two matvecs.  The
+    initialisation (r = f - B x0, p = r, rs, thr2, stat[0]) is torch ops, once per solve; ``part`` and ``state`` serve every step.
+    stat[0] takes the maximum with the first relative residual, stat[1] the count of steps with p^T B p <= 0."""
+    shape = f.shape
+    v = x0.clone(memory_format=torch.contiguous_format).reshape(-1)
+    fv = f.reshape(-1)
+    r = fv - local_matvec(Phi, Ak, Psi, x0).reshape(-1)
+    p = r.clone()
+    rs = torch.dot(r, r)
+    fn2 = torch.dot(fv, fv)
+    stat[0:1].copy_(torch.maximum(stat[0:1], torch.sqrt(rs / fn2.clamp_min(torch.finfo(f.dtype).tiny)).reshape(1)))
+    state = torch.zeros(8, dtype=torch.float64, device=f.device)
+    state[0:1].copy_(rs.reshape(1))
+    state[2:3].copy_(((rel * rel) * fn2).reshape(1))
+    part = torch.empty((2, cg_parts(f.dtype, v.numel())), dtype=torch.float64, device=f.device)
+    for step in range(iters):
+        Bp = local_matvec(Phi, Ak, Psi, p.view(shape)).reshape(-1)
+        cg_dot(p, Bp, part)
+        cg_update(step, p, Bp, v, r, part, state)
+        cg_direction(step, r, p, part, state)
+    stat[1:2].add_(state[3:4].to(stat.dtype))
+    return v.view(shape)

@@ -1214,3 +1214,77 @@ def ritz_update(mode: int, which: int, first: int, rel: float, part: torch.Tenso
     sweep[1:2].add_((flags != 0).to(sweep.dtype).reshape(1))
     sweep[2:3].copy_(theta.reshape(1))
     sweep[3:4].copy_(torch.where((sweep[3:4] == flags) | (flags == 0), sweep[3:4], torch.where(sweep[3:4] == 0, flags, 3.0 * one)).reshape(1))
+
+
+# ---------------------------------------------------------------------------------------------- tt_amen_solve (ttamen.py)
+# Mirror of ttr_cg.hip: one conjugate-gradient step in three calls on the vectors v, r, p, Bp, with the scalars in an fp64 state
+# of 8 words (rs slot 0, rs slot 1, thr2, bad, live, alpha, pBp, beta; include/ttround_hip.h).  Written without a branch on a value,
+# so that the same code on device tensors is the torch baseline of tools/amen_bench.py.
+def cg_parts(dtype: torch.dtype, n: int) -> int:
+    """The columns of ``part``: the mirror sums in one piece."""
+    return 1
+
+
+def cg_workspace_bytes(dtype: torch.dtype, n: int) -> int:
+    return 2 * 8 * cg_parts(dtype, n)
+
+
+def _row_sum(row: torch.Tensor) -> torch.Tensor:
+    s = row[0].clone()
+    for g in range(1, row.shape[0]):
+        s = s + row[g]
+    return s
+
+
+def cg_dot(p: torch.Tensor, Bp: torch.Tensor, part: torch.Tensor) -> None:
+    """part[0] (of an fp64 [2, parts]) = the shares of p . Bp in fp64: here one share, the rest zeros."""
+    part[0].zero_()
+    part[0, 0:1].copy_(torch.dot(p.double(), Bp.double()).reshape(1))
+
+
+def cg_update(step: int, p: torch.Tensor, Bp: torch.Tensor, v: torch.Tensor, r: torch.Tensor, part: torch.Tensor,
+              state: torch.Tensor) -> None:
+    """Mirror of ttr_cg_update, in place.  pBp is the sum of part[0] in the order of its entries; with rs = state[step & 1] and
+    thr2 = state[2]: live = (rs > thr2) & (pBp > 0), alpha = rs / pBp where live, else 0; v += alpha p and r -= alpha Bp in fp64,
+    rounded once, only where live; part[1] = the shares of r . r of the rounded r (zeros where not live); state[3] += 1 for an
+    active step with pBp <= 0, state[4:7] = live, alpha, pBp."""
+    dt, slot = v.dtype, int(step) & 1
+    pBp = _row_sum(part[0])
+    rs, thr2 = state[slot], state[2]
+    one, zero = torch.ones_like(pBp), torch.zeros_like(pBp)
+    active, good = rs > thr2, pBp > 0
+    live = active & good
+    alpha = torch.where(live, rs / torch.where(good, pBp, one), zero)
+    vn = torch.addcmul(v.double(), p.double(), alpha).to(dt)
+    rn = torch.addcmul(r.double(), Bp.double(), -alpha).to(dt)
+    v.copy_(torch.where(live, vn, v))
+    r.copy_(torch.where(live, rn, r))
+    part[1].zero_()
+    part[1, 0:1].copy_(torch.where(live, torch.dot(rn.double(), rn.double()), zero).reshape(1))
+    state[3:4].add_((active & ~good).to(state.dtype).reshape(1))
+    state[4:7].copy_(torch.stack([live.to(state.dtype), alpha, pBp]))
+
+
+def cg_direction(step: int, r: torch.Tensor, p: torch.Tensor, part: torch.Tensor, state: torch.Tensor) -> None:
+    """Mirror of ttr_cg_direction, in place.  rs' is the sum of part[1]; where the step was live (state[4]):
+    beta = rs' / max(rs, tiny of the dtype), p = r + beta p in fp64, rounded once, and the other rs slot takes rs'; where it was
+    not, p stays, beta = 0 and the slot takes rs.  state[7] = beta."""
+    dt, slot = p.dtype, int(step) & 1
+    rsn = _row_sum(part[1])
+    rs = state[slot]
+    live = state[4] != 0
+    zero = torch.zeros_like(rs)
+    beta = torch.where(live, rsn / rs.clamp_min(float(torch.finfo(dt).tiny)), zero)
+    pn = torch.addcmul(r.double(), p.double(), beta).to(dt)
+    p.copy_(torch.where(live, pn, p))
+    state[1 - slot:2 - slot].copy_(torch.where(live, rsn, rs).reshape(1))
+    state[7:8].copy_(beta.reshape(1))
+
+
+def cg_solve(Phi, Ak, Psi, f, x0, rel: float, iters: int, stat: torch.Tensor) -> torch.Tensor:
+    """The local solve of tt_amen_solve on the CPU: ``ttsolve._cg`` itself, the specification of the kernels."""
+    import sys
+
+    from .ttsolve import _cg
+
+    return _cg(sys.modules[__name__], Phi, Ak, Psi, f, x0, rel, iters, stat)

@@ -15,6 +15,7 @@
 // Every index is bounded by n; `part` is bounded by workspace_bytes (checked on the host); state and sweep are 8 and 4 doubles.
 // No atomics, no cooperative launch: the two launches are ordered by the stream.
 #include "detail/ttr_internal.h"
+#include "detail/ttr_pack_io.h"
 
 namespace ttr {
 
@@ -25,31 +26,6 @@ inline int ritz_parts(int dtype, int64_t n) {
   const int64_t V = 16 / elem_size(dtype);
   const int64_t g = ceil_div(ceil_div(n, V), (int64_t)kThreads * kRitzPacksPerThread);
   return (int)(g < 1 ? 1 : (g > TTR_RITZ_MAX_PARTS ? TTR_RITZ_MAX_PARTS : g));
-}
-
-// elements [base, base + V) of x as one pack: one 16-byte load where WIDE and the pack lies inside n, element by element (zeros
-// past n) otherwise
-template <typename T, int V, bool WIDE>
-__device__ __forceinline__ Pack<T, V> ritz_load(const T* __restrict__ x, int64_t base, int64_t n) {
-  Pack<T, V> p;
-  if (WIDE && base + V <= n) {
-    p = *reinterpret_cast<const Pack<T, V>*>(x + base);
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v) p.v[v] = base + v < n ? x[base + v] : T(0);
-  }
-  return p;
-}
-
-template <typename T, int V, bool WIDE>
-__device__ __forceinline__ void ritz_store(T* __restrict__ x, int64_t base, int64_t n, const Pack<T, V>& p) {
-  if (WIDE && base + V <= n) {
-    *reinterpret_cast<Pack<T, V>*>(x + base) = p;
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-      if (base + v < n) x[base + v] = p.v[v];
-  }
 }
 
 // KIND 0: TTR_RITZ_INIT (X, AX only); 1: a step whose P is zero (P, AP not read); 2: a step
@@ -66,15 +42,15 @@ __global__ __launch_bounds__(kThreads) void ritz_gram_kernel(int64_t n, const T*
   const int64_t npacks = (n + V - 1) / V;
   for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < npacks; p += (int64_t)gridDim.x * kThreads) {
     const int64_t base = p * V;
-    const Pack<T, V> x = ritz_load<T, V, WIDE>(X, base, n), ax = ritz_load<T, V, WIDE>(AX, base, n);
+    const Pack<T, V> x = pack_load<T, V, WIDE>(X, base, n), ax = pack_load<T, V, WIDE>(AX, base, n);
     Pack<T, V> w, aw, pp, ap;
     if (KIND >= 1) {
-      w = ritz_load<T, V, WIDE>(W, base, n);
-      aw = ritz_load<T, V, WIDE>(AW, base, n);
+      w = pack_load<T, V, WIDE>(W, base, n);
+      aw = pack_load<T, V, WIDE>(AW, base, n);
     }
     if (KIND == 2) {
-      pp = ritz_load<T, V, WIDE>(P, base, n);
-      ap = ritz_load<T, V, WIDE>(AP, base, n);
+      pp = pack_load<T, V, WIDE>(P, base, n);
+      ap = pack_load<T, V, WIDE>(AP, base, n);
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -257,7 +233,7 @@ __global__ __launch_bounds__(kThreads) void ritz_update_kernel(int mode, int whi
   const int64_t npacks = (n + V - 1) / V;
   for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < npacks; p += (int64_t)gridDim.x * kThreads) {
     const int64_t base = p * V;
-    Pack<T, V> x = ritz_load<T, V, WIDE>(X, base, n), ax = ritz_load<T, V, WIDE>(AX, base, n);
+    Pack<T, V> x = pack_load<T, V, WIDE>(X, base, n), ax = pack_load<T, V, WIDE>(AX, base, n);
     Pack<T, V> w, pn, apn;
     if (mode == TTR_RITZ_INIT) {
 #pragma unroll
@@ -269,11 +245,11 @@ __global__ __launch_bounds__(kThreads) void ritz_update_kernel(int mode, int whi
       }
       apn = pn;
     } else {
-      const Pack<T, V> w0 = ritz_load<T, V, WIDE>(W, base, n), aw = ritz_load<T, V, WIDE>(AW, base, n);
+      const Pack<T, V> w0 = pack_load<T, V, WIDE>(W, base, n), aw = pack_load<T, V, WIDE>(AW, base, n);
       Pack<T, V> p0, ap0;
       if (HASP) {
-        p0 = ritz_load<T, V, WIDE>(P, base, n);
-        ap0 = ritz_load<T, V, WIDE>(AP, base, n);
+        p0 = pack_load<T, V, WIDE>(P, base, n);
+        ap0 = pack_load<T, V, WIDE>(AP, base, n);
       }
 #pragma unroll
       for (int v = 0; v < V; ++v) {
@@ -289,12 +265,12 @@ __global__ __launch_bounds__(kThreads) void ritz_update_kernel(int mode, int whi
         w.v[v] = (T)fma(-theta, (double)x.v[v], (double)ax.v[v]);   // of the ROUNDED X and AX: the residual of what is stored
       }
     }
-    ritz_store<T, V, WIDE>(X, base, n, x);
-    ritz_store<T, V, WIDE>(AX, base, n, ax);
-    ritz_store<T, V, WIDE>(W, base, n, w);
+    pack_store<T, V, WIDE>(X, base, n, x);
+    pack_store<T, V, WIDE>(AX, base, n, ax);
+    pack_store<T, V, WIDE>(W, base, n, w);
     if (HASP) {
-      ritz_store<T, V, WIDE>(P, base, n, pn);
-      ritz_store<T, V, WIDE>(AP, base, n, apn);
+      pack_store<T, V, WIDE>(P, base, n, pn);
+      pack_store<T, V, WIDE>(AP, base, n, apn);
     }
   }
 }

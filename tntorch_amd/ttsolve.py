@@ -21,8 +21,9 @@ Conjugate gradients run with no host synchronisation: the iteration count is fix
 system that has converged has its ``alpha`` forced to 0 so the remaining iterations change nothing.  One readback per sweep
 fetches the largest local residual and the flag of a lost positive definiteness.
 
-Not here: rank adaptation (AMEn enrichment, two-site DMRG), nonsymmetric local solvers (GMRES), a preconditioner for the local
-CG, a fused kernel for CG's vector updates (torch does them), the variational ``tt_apply`` that the same kernel with bra != ket
+Not here: rank adaptation (AMEn enrichment is ``tt_amen_solve``, ttamen.py, which shares the checks and helpers below; two-site
+DMRG), nonsymmetric local solvers (GMRES), a preconditioner for the local CG, a fused kernel for CG's vector updates (torch
+does them here; ``tt_amen_solve`` has one), the variational ``tt_apply`` that the same kernel with bra != ket
 would serve, eigenvalue solvers, batched operands and the device backward.
 """
 
@@ -140,6 +141,18 @@ def tt_solve(tt_matrix, b, transpose: bool = False, x0: Optional[Tensor] = None,
     The call runs under ``torch.no_grad()`` and returns detached cores; on the device an operand that requires grad raises
     ``NotImplementedError`` under grad mode."""
     who = "tt_solve"
+    G, trains = _check_system(who, tt_matrix, b, x0)
+    if x0 is None and ranks_tt is None:
+        raise ValueError("{}: give x0 or ranks_tt (the ranks of the solution are fixed)".format(who))
+    _check_controls(who, nswp, local_iters, tol)
+    _check_devices(who, G, trains)
+    with torch.no_grad():
+        return _solve(tt_matrix, b, bool(transpose), x0, ranks_tt, int(nswp), tol, int(local_iters), verbose, return_info)
+
+
+def _check_system(who: str, tt_matrix, b, x0):
+    """The operand checks of the TT solvers (tt_solve, tt_amen_solve), in their order: the matrix, then ``b`` and ``x0`` (class,
+    batch, CP cores, modes, boundary ranks), then square modes of one size.  Returns the matrix cores and the named trains."""
     G = _matrix_cores(who, "the first argument", tt_matrix)
     N = len(G)
     trains = [("b", b)] + ([("x0", x0)] if x0 is not None else [])
@@ -149,7 +162,7 @@ def tt_solve(tt_matrix, b, transpose: bool = False, x0: Optional[Tensor] = None,
         if t.batch:
             raise ValueError("{}: batched tensors are not supported ({})".format(who, name))
         if any(c.dim() == 2 for c in t.cores):
-            _not_in_scope("tt_solve with CP cores")
+            _not_in_scope("{} with CP cores".format(who))
         if t.dim() != N:
             raise ValueError("{}: the matrix has {} modes, {} has {}".format(who, N, name, t.dim()))
         if t.cores[0].shape[0] != 1 or t.cores[-1].shape[-1] != 1:
@@ -161,19 +174,23 @@ def tt_solve(tt_matrix, b, transpose: bool = False, x0: Optional[Tensor] = None,
         for name, t in trains:
             if int(t.shape[k]) != int(g.shape[1]):
                 raise ValueError("{}: mode {} of {} has size {}, the matrix's {}".format(who, k, name, int(t.shape[k]), int(g.shape[1])))
-    if x0 is None and ranks_tt is None:
-        raise ValueError("{}: give x0 or ranks_tt (the ranks of the solution are fixed)".format(who))
+    return G, trains
+
+
+def _check_controls(who: str, nswp, local_iters, tol) -> None:
     if int(nswp) < 1 or int(local_iters) < 1:
         raise ValueError("{}: nswp and local_iters must be at least 1, got {} and {}".format(who, nswp, local_iters))
     if tol is not None and not float(tol) > 0:
         raise ValueError("{}: tol must be positive, got {}".format(who, tol))
+
+
+def _check_devices(who: str, G, trains) -> None:
+    """One device and dtype for the matrix and the trains; on the device under grad mode an operand that requires grad is refused."""
     tensors = []
     for _, t in trains:
         tensors += list(t.cores) + [U for U in t.Us if U is not None]
     if _check_operands(who, G, tensors) and torch.is_grad_enabled():
         _refuse_device_grad(who)
-    with torch.no_grad():
-        return _solve(tt_matrix, b, bool(transpose), x0, ranks_tt, int(nswp), tol, int(local_iters), verbose, return_info)
 
 
 def _solve(tt_matrix, b, transpose, x0, ranks_tt, nswp, tol, local_iters, verbose, return_info):
