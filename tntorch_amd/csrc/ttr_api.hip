@@ -502,7 +502,8 @@ int ttr_project_flat(int dtype, int64_t R, int64_t n, int64_t ro, int64_t batch,
                      void* left, int64_t ldl, int64_t strideL, const int32_t* rows32, const int32_t* flat, const void* sigma1,
                      int64_t stride_sigma1, void* stream) {
   TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_project: bad dtype %d", dtype);
-  TTR_REQUIRE(R >= 1 && n >= 1 && ro >= 1 && batch >= 0, TTR_E_INVALID, "ttr_project: bad shape");
+  // (ro outside [1, R] is a matter of the kernels' envelope: TTR_E_UNSUPPORTED from the dispatcher, like ro > R)
+  TTR_REQUIRE(R >= 1 && n >= 1 && batch >= 0, TTR_E_INVALID, "ttr_project: bad shape");
   if (batch == 0) return TTR_OK;
   TTR_REQUIRE(M && V2 && right, TTR_E_INVALID, "ttr_project: null pointer");
   TTR_REQUIRE(!scale_right || sigma, TTR_E_INVALID, "ttr_project: scale_right needs sigma");
@@ -541,7 +542,7 @@ int ttr_colproject(int dtype, int64_t rows, int64_t n, int64_t ro, int64_t batch
                    int64_t strideV2, const void* sigma, int64_t stride_sigma, int left_ortho, void* left, int64_t ldl,
                    int64_t strideL, void* right, int64_t ldr, int64_t strideR, void* stream) {
   TTR_REQUIRE(dtype_ok(dtype), TTR_E_INVALID, "ttr_colproject: bad dtype %d", dtype);
-  TTR_REQUIRE(rows >= 1 && n >= 1 && ro >= 1 && batch >= 0, TTR_E_INVALID, "ttr_colproject: bad shape");
+  TTR_REQUIRE(rows >= 1 && n >= 1 && batch >= 0, TTR_E_INVALID, "ttr_colproject: bad shape");   // (ro: as ttr_project's)
   if (batch == 0) return TTR_OK;
   TTR_REQUIRE(M && V2 && left, TTR_E_INVALID, "ttr_colproject: null pointer");
   TTR_REQUIRE(!left_ortho || sigma, TTR_E_INVALID, "ttr_colproject: left_ortho needs sigma");

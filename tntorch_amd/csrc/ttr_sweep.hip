@@ -826,10 +826,13 @@ __global__ __launch_bounds__(kThreads, (sizeof(T) == 4 ? (ROT ? 3 : 4) : 1)) voi
   }
 }
 
-// out[b][e] = sum_p in[b][p][e]  (fixed order: deterministic)
+// out[b][e] = sum_p in[b][p][e]  (fixed order: deterministic).  skip[b] != 0 (colgram_kernel's flags, same item numbering): the item's
+// partials were never written -- they are not read, and out[b] is not written
 template <typename T>
-__global__ __launch_bounds__(kThreads) void sum_parts_kernel(const T* __restrict__ in, T* __restrict__ out, int parts, int64_t count) {
+__global__ __launch_bounds__(kThreads) void sum_parts_kernel(const T* __restrict__ in, T* __restrict__ out, int parts, int64_t count,
+                                                             const int32_t* __restrict__ skip) {
   const int64_t b = blockIdx.y;
+  if (skip && skip[b] != 0) return;  // (block-uniform)
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < count; e += (int64_t)gridDim.x * kThreads) {
     T s = T(0);
     for (int q = 0; q < parts; ++q) s += in[((int64_t)b * parts + q) * count + e];
@@ -986,7 +989,7 @@ static int colgram_typed(int64_t rows, int64_t n, int64_t batch, const void* Mx,
     if (sp > 1) {
       int64_t gx = ceil_div(n * n, kThreads);
       hipLaunchKernelGGL(sum_parts_kernel<T>, dim3((unsigned)gx, (unsigned)nb), dim3(kThreads), 0, stream,
-                         (const T*)q.G, (T*)G + b0 * n * n, sp, n * n);
+                         (const T*)q.G, (T*)G + b0 * n * n, sp, n * n, q.skip);
     }
   }
   TTR_HIP_CHECK(hipGetLastError());
